@@ -7,6 +7,13 @@ multiplicative V(1,1) cycle with weighted Jacobi (w = 0.8) over the whole
 2-norm.  Inputs (matrices, RHS, iterate) are resident in HBM before the timed
 region.  Scaling is strong: the 512^3 problem is split into z-slabs across
 ranks.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs
+when --dump-outputs is given, and prints the line (the fine kernels' event
+times come out of the timed loop itself).  Every other leg -- the parity check
+against the oracle, the CPU baselines, the fine-grid SpMV rates, STREAM triad,
+the general-CSR V-cycle and the asynchronous-smoother overlap -- runs with
+--full only.
 """
 import argparse
 import json
@@ -34,6 +41,14 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--n", type=int, default=512)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beyond the headline: parity against the oracle, CPU baselines, "
+                        "fine-grid SpMV rates, STREAM triad, the general-CSR V-cycle, the async-smoother overlap "
+                        "(each still under its own switch below)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step left a caller -- the iterate u and the "
+                        "residual norms [|r_0|, |r_last|] -- as DIR/<name>.npy (float64; an iterate larger than "
+                        "the budget as a fixed seeded sample of its entries)")
     p.add_argument("--smooth-weight", type=float, default=0.8)
     p.add_argument("--reuse-outer-residual", type=int, default=2)
     p.add_argument("--cpu-baseline", type=int, default=1)
@@ -58,6 +73,26 @@ def parse():
                    help="distributed hierarchy: z-slab extended operators (default) or the "
                         "row-partitioned [owned | ghost] CSR form")
     return p.parse_args()
+
+
+DUMP_MAX_ENTRIES = 1 << 22  # per array: 32 MiB of float64, two such stay under the 64 MB budget
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64.  An array of
+    more than DUMP_MAX_ENTRIES entries is written as the entries at a fixed
+    sample of indices (default_rng(0), sorted), the same for every run of the
+    same size, so that two builds compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_MAX_ENTRIES:
+            a = a[np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ENTRIES))]
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 * 10 ** 6, total
+    log(f"[dump] {', '.join(arrays)} -> {path} ({total / 1e6:.1f} MB)")
 
 
 def storage(nrows, nnz, vi, dc, rp, pp=0, mp=0):
@@ -398,6 +433,55 @@ def check_parity(u_par, u_cpu, rel_cpu, cycles):
             "relres_rtol_ok": bool(abs(rel_gpu - rel_cpu) <= 1e-12 * abs(rel_cpu))}
 
 
+def fine_spmv_rates(amg, ctx, gen, A0, mat_bytes, fmt, args):
+    """--full: the fine-grid SpMV y = A0 x in the headline's format and in the
+    general formats, and STREAM triad, each a timed run of its own (HIP events
+    on the compute stream).  Returns (fine_spmv, {"csr", "csr_vi"}, triad GB/s)."""
+    import ctypes as C
+    n0, z0 = A0.nrows, A0.nnz
+    # fine-grid SpMV y = A x (SURVEY.md Sec.8(d): matrix + x + y), events on the same stream
+    x = ctx.vec(n0)
+    x.set(1.0)
+    y = ctx.vec(n0)
+    spmv_ms = C.c_double()
+    amg.check(amg.lib.amg_matvec_timed(ctx.h, A0.h, x.h, y.h, args.spmv_reps, C.byref(spmv_ms)))
+    spmv_bytes = mat_bytes + 16 * n0
+    spmv_gbs = spmv_bytes / (spmv_ms.value * 1e-3) / 1e9
+    # the general kernels on the same operator: A0 registered again with the
+    # compressed forms off (plain CSR, the reference's storage) and with only the
+    # value index on (CSR-VI), timed the same way -- the kernels an unstructured
+    # (BoomerAMG / elasticity) hierarchy runs
+    general = {}
+    for tag, vi in (("csr", 0), ("csr_vi", 1)):
+        ctx.set_value_index(vi)
+        ctx.set_dict_index(0)
+        ctx.set_row_pattern(0)
+        ctx.set_pair_pattern(0)
+        ctx.set_master_pattern(0)
+        Ag = gen.register(ctx, amg.AMG_GEN_A, 0)
+        gms = C.c_double()
+        amg.check(amg.lib.amg_matvec_timed(ctx.h, Ag.h, x.h, y.h, args.spmv_reps, C.byref(gms)))
+        gb, gfmt = storage(n0, z0, Ag.value_index, 0, 0)
+        gbytes = gb + 16 * n0
+        general[tag] = {"format": gfmt, "ms": gms.value, "bytes": gbytes,
+                        "gbs": gbytes / (gms.value * 1e-3) / 1e9,
+                        "frac": gbytes / (gms.value * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        log(f"[gpu] fine SpMV {gfmt}: {gms.value:.3f} ms ({general[tag]['gbs']:.0f} GB/s)")
+        Ag.free()
+    for fn in (ctx.set_value_index, ctx.set_dict_index, ctx.set_row_pattern, ctx.set_pair_pattern,
+               ctx.set_master_pattern):
+        fn(1)
+    # practical ceiling: STREAM triad over three 2 GiB arrays on the same device
+    triad = C.c_double()
+    amg.check(amg.lib.amg_stream_triad(ctx.h, 1 << 28, 10, C.byref(triad)))
+    log(f"[gpu] STREAM triad {triad.value:.0f} GB/s")
+    log(f"[gpu] fine SpMV {spmv_ms.value:.3f} ms ({spmv_gbs:.0f} GB/s)")
+    x.free()
+    y.free()
+    return ({"gbs": spmv_gbs, "ms": spmv_ms.value, "bytes": spmv_bytes, "frac": spmv_gbs / HBM_PEAK_GBS,
+             "format": fmt}, general, triad.value)
+
+
 def launch_ranks(args):
     """`bench.py --gpus N` with N > 1 outside torchrun: start torchrun with N ranks
     as a child process (nothing here has touched the GPU yet) and exit with its
@@ -464,8 +548,12 @@ def main():
     dt = t2 - t1
     value = args.steps / dt
     log(f"[gpu] {args.steps} steps in {dt * 1e3:.2f} ms -> {value:.2f} it/s; relres {rn / r0:.3e}")
+    if args.dump_outputs:
+        # what the last timed step left a caller: the iterate and the residual norms
+        H.get_u(u0)
+        dump_outputs(args.dump_outputs, {"u": u0.download(), "resnorm": np.array([r0, rn])})
     u_par = None
-    if args.cpu_baseline:
+    if args.full and args.cpu_baseline:
         # parity leg (untimed): restart the same solve and run exactly the
         # oracle's cpu_cycles outer iterations, keep the iterate for the check
         u0.set(0.0)
@@ -483,76 +571,40 @@ def main():
     fused_prolong = H.fused_prolong
     fused_outer = H.fused_outer
     plane_march = As[0].plane_march
+    march_points = [A.march_points for A in As]
     kernels = fine_kernels(n0, mat_bytes, ms, launches, fused, fmt, fused_prolong, fused_outer)
-    # fine-grid SpMV y = A x (matrix + x + y), events on the same stream
-    x = ctx.vec(n0)
-    x.set(1.0)
-    y = ctx.vec(n0)
-    import ctypes as C
-    spmv_ms = C.c_double()
-    amg.check(amg.lib.amg_matvec_timed(ctx.h, As[0].h, x.h, y.h, args.spmv_reps, C.byref(spmv_ms)))
-    spmv_bytes = mat_bytes + 16 * n0
-    spmv_gbs = spmv_bytes / (spmv_ms.value * 1e-3) / 1e9
-    # the general kernels on the same operator: A0 registered again with the
-    # compressed forms off (plain CSR, the reference's storage) and with only the
-    # value index on (CSR-VI), timed the same way -- the kernels an unstructured
-    # (BoomerAMG / elasticity) hierarchy runs
-    general = {}
-    for tag, vi in (("csr", 0), ("csr_vi", 1)):
-        ctx.set_value_index(vi)
-        ctx.set_dict_index(0)
-        ctx.set_row_pattern(0)
-        ctx.set_pair_pattern(0)
-        ctx.set_master_pattern(0)
-        Ag = gen.register(ctx, amg.AMG_GEN_A, 0)
-        gms = C.c_double()
-        amg.check(amg.lib.amg_matvec_timed(ctx.h, Ag.h, x.h, y.h, args.spmv_reps, C.byref(gms)))
-        gb, gfmt = storage(n0, z0, Ag.value_index, 0, 0)
-        gbytes = gb + 16 * n0
-        general[tag] = {"format": gfmt, "ms": gms.value, "bytes": gbytes,
-                        "gbs": gbytes / (gms.value * 1e-3) / 1e9,
-                        "frac": gbytes / (gms.value * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        log(f"[gpu] fine SpMV {gfmt}: {gms.value:.3f} ms ({general[tag]['gbs']:.0f} GB/s)")
-        Ag.free()
-    for fn in (ctx.set_value_index, ctx.set_dict_index, ctx.set_row_pattern, ctx.set_pair_pattern,
-               ctx.set_master_pattern):
-        fn(1)
-    # practical ceiling: STREAM triad over three 2 GiB arrays on the same device
-    triad = C.c_double()
-    amg.check(amg.lib.amg_stream_triad(ctx.h, 1 << 28, 10, C.byref(triad)))
-    log(f"[gpu] STREAM triad {triad.value:.0f} GB/s")
+    spmv, general, triad = None, {}, None
+    if args.full:
+        spmv, general, triad = fine_spmv_rates(amg, ctx, gen, As[0], mat_bytes, fmt, args)
     for k, v in kernels.items():
-        log(f"[gpu] {k}: {v['ms']:.3f} ms, {v['gbs']:.0f} GB/s ({v['frac']:.3f} of peak, "
-            f"{v['gbs'] / triad.value:.3f} of triad)")
-    log(f"[gpu] fine SpMV {spmv_ms.value:.3f} ms ({spmv_gbs:.0f} GB/s)")
+        log(f"[gpu] {k}: {v['ms']:.3f} ms, {v['gbs']:.0f} GB/s ({v['frac']:.3f} of peak"
+            + (f", {v['gbs'] / triad:.3f} of triad)" if triad else ")"))
     dom = max(kernels, key=lambda k: kernels[k]["ms"])
     dk = kernels[dom]
     roofline = {"bound": "hbm", "kernel": f"{dom}: {dk['what']}", "achieved": dk["gbs"], "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": dk["frac"], "traffic": load_traffic(n, dom),
                 "alg_bytes_per_launch": dk["bytes"], "avg_launch_ms": dk["ms"],
-                "frac_of_stream_triad": dk["gbs"] / triad.value,
+                "frac_of_stream_triad": dk["gbs"] / triad if triad else None,
                 "selection": "the fine-level kernel with the largest time per step (fine_kernels)"}
-    x.free()
-    y.free()
     H.free()
     for M in As + Ps + Rs:
         M.free()
     ctx.close()
 
     ajac = None
-    if args.ajac_ranks > 1:
+    if args.full and args.ajac_ranks > 1:
         try:
             ajac = async_jacobi_overlap(args)
         except Exception as e:  # noqa: BLE001
             log(f"[ajac] failed: {e!r}")
     vgen = None
-    if args.general:
+    if args.full and args.general:
         try:
             vgen = general_csr_vcycle(amg, gen, f_host, args)
         except Exception as e:  # noqa: BLE001
             log(f"[general] failed: {e!r}")
     cpu, parity, seq = None, None, None
-    if args.cpu_baseline:
+    if args.full and args.cpu_baseline:
         # OMP_PROC_BIND=close for the SMEM leg; read by
         # libgomp when the oracle library loads, which happens below
         os.environ.setdefault("OMP_PROC_BIND", "close")
@@ -587,28 +639,31 @@ def main():
                    "n": n, "levels": L, "nnz_A0": z0, "rows": n0,
                    "reuse_outer_residual": args.reuse_outer_residual,
                    "matrix_format": fmt, "plane_march": plane_march,
-                   "march_points": [A.march_points for A in As], "geometric_transfers": fused,
+                   "march_points": march_points, "geometric_transfers": fused,
                    "fused_prolong_sweep": fused_prolong,
                    "fused_post_sweep_outer_residual": fused_outer,
                    "parallelism": "single GPU"},
-        "fine_spmv": {"gbs": spmv_gbs, "ms": spmv_ms.value, "bytes": spmv_bytes,
-                      "frac": spmv_gbs / HBM_PEAK_GBS, "format": fmt},
-        "fine_spmv_csr": general["csr"],
-        "fine_spmv_csr_vi": general["csr_vi"],
-        "roofline_csr": {"bound": "hbm", "kernel": "fine-grid SpMV y = A0 x, plain CSR tile kernel",
-                         "achieved": general["csr"]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": general["csr"]["frac"], "alg_bytes_per_launch": general["csr"]["bytes"],
-                         "avg_launch_ms": general["csr"]["ms"]},
-        "stream_triad_gbs": triad.value,
+        "full": bool(args.full),
         "roofline": roofline,
         "fine_kernels": kernels,
-        "cpu_baseline": cpu,
-        "cpu_baseline_seq": seq,
-        "vcycle_general_csr": vgen,
-        "async_jacobi_overlap": ajac,
-        "parity": parity,
         "final_relres": rn / r0,
     }
+    if args.full:
+        out.update({
+            "fine_spmv": spmv,
+            "fine_spmv_csr": general["csr"],
+            "fine_spmv_csr_vi": general["csr_vi"],
+            "roofline_csr": {"bound": "hbm", "kernel": "fine-grid SpMV y = A0 x, plain CSR tile kernel",
+                             "achieved": general["csr"]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": general["csr"]["frac"], "alg_bytes_per_launch": general["csr"]["bytes"],
+                             "avg_launch_ms": general["csr"]["ms"]},
+            "stream_triad_gbs": triad,
+            "cpu_baseline": cpu,
+            "cpu_baseline_seq": seq,
+            "vcycle_general_csr": vgen,
+            "async_jacobi_overlap": ajac,
+            "parity": parity,
+        })
     print(json.dumps(out), flush=True)
 
 

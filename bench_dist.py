@@ -92,23 +92,39 @@ def main(args, world, rank):
         kernels = fine_kernels(D.n0, mat_bytes, ms, launches, fmask, fmt)
     all_k = [None] * world
     tdist.all_gather_object(all_k, kernels)
-    u_par = None
-    if args.cpu_baseline:
-        # parity leg (untimed): restart and run exactly the oracle's cpu_cycles
-        # outer iterations; rank 0 gathers the slabs of the iterate
-        r0p = D.solve_start(f)
-        D.iterate(args.cpu_cycles)
-        rel_p = D.resnorm() / r0p
+
+    def gather_u():
+        """the slabs of the iterate on rank 0 (None elsewhere)"""
         u_loc = torch.from_numpy(D.get_u())
         sizes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
         tdist.all_gather(sizes, torch.tensor([u_loc.numel()], dtype=torch.int64))
         if rank == 0:
             parts = [torch.empty(int(sz.item()), dtype=torch.float64) for sz in sizes]
             tdist.gather(u_loc, parts, dst=0)
-            u_par = (torch.cat(parts).numpy(), rel_p)
-        else:
-            tdist.gather(u_loc, None, dst=0)
-    spmv_ms = D.fine_spmv_ms(args.spmv_reps)
+            return torch.cat(parts).numpy()
+        tdist.gather(u_loc, None, dst=0)
+        return None
+
+    full = args.full
+    if args.dump_outputs:
+        # what the last timed step left a caller: the iterate and the residual norms
+        u_last = gather_u()
+        if rank == 0:
+            from bench import dump_outputs
+            dump_outputs(args.dump_outputs, {"u": u_last, "resnorm": np.array([r0, rn])})
+        del u_last
+    u_par = None
+    if full and args.cpu_baseline:
+        # parity leg (untimed): restart and run exactly the oracle's cpu_cycles
+        # outer iterations; rank 0 gathers the slabs of the iterate
+        r0p = D.solve_start(f)
+        D.iterate(args.cpu_cycles)
+        rel_p = D.resnorm() / r0p
+        u_all = gather_u()
+        if rank == 0:
+            u_par = (u_all, rel_p)
+    # the fine SpMV is a timed run of its own: --full only
+    spmv_ms = D.fine_spmv_ms(args.spmv_reps) if full else float("nan")
     spmv_bytes = mat_bytes + 16 * D.n0
     # aggregate fine SpMV rate: all ranks' algorithmic bytes over the slowest rank's time
     agg = torch.tensor([float(spmv_bytes), spmv_ms, float(res_bytes), res_ms], dtype=torch.float64)
@@ -119,7 +135,7 @@ def main(args, world, rank):
     amg.dist.finalize(ctx)
     ctx.close()
     cpu, parity = None, None
-    if rank == 0 and args.cpu_baseline:
+    if rank == 0 and full and args.cpu_baseline:
         from bench import cpu_baseline, check_parity
         try:
             cpu, u_cpu, rel_cpu = cpu_baseline(gen, amg, amg.rhs_rand(0, n ** 3), args)
@@ -154,7 +170,7 @@ def main(args, world, rank):
                     "alg_bytes_per_launch": res_bytes, "avg_launch_ms": res_ms,
                     "aggregate_gbs": res_gbs}
         log(f"[dist] {args.steps} steps in {dt * 1e3:.2f} ms -> {value:.2f} it/s; relres {rn / r0:.3e}; "
-            f"fine SpMV aggregate {spmv_gbs:.0f} GB/s")
+            + (f"fine SpMV aggregate {spmv_gbs:.0f} GB/s" if full else "fine SpMV not timed (--full)"))
         out = {
             "metric": METRIC,
             "value": value,
@@ -178,8 +194,9 @@ def main(args, world, rank):
                        "geometric_transfer_levels": geo_mask if slab else None,
                        "fused_residual_restriction": bool(fused0) if slab else None,
                        "reuse_outer_residual": args.reuse_outer_residual},
+            "full": bool(full),
             "fine_spmv": {"gbs_aggregate": spmv_gbs, "ms_max": float(P[:, 1].max()),
-                          "frac_per_gpu": spmv_gbs / world / HBM_PEAK_GBS},
+                          "frac_per_gpu": spmv_gbs / world / HBM_PEAK_GBS} if full else None,
             "roofline": roof,
             "fine_kernels": kernels,
             # the CPU baseline is reported at N = 1 only (the oracle still runs at

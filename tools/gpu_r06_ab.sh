@@ -13,7 +13,7 @@ for v in "$@"; do
   tag=$(echo "$v" | tr ' =' '_-')
   envs=""; [ "$v" != "-" ] && envs="$v"
   d=$O/p_${tag}_$rep
-  env $envs timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o run -- python3 bench.py --steps 20 --warmup 3 --cpu-baseline 0 --general 0 --spmv-reps 5 > $O/b_${tag}_$rep.json 2> $O/b_${tag}_$rep.err || { echo "variant $v failed"; tail -5 $O/b_${tag}_$rep.err; exit 1; }
+  env $envs timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o run -- python3 bench.py --full --steps 20 --warmup 3 --cpu-baseline 0 --general 0 --spmv-reps 5 > $O/b_${tag}_$rep.json 2> $O/b_${tag}_$rep.err || { echo "variant $v failed"; tail -5 $O/b_${tag}_$rep.err; exit 1; }
   s=$(find $d -name "*kernel_stats.csv" | head -1)
   python3 - "$v" "$O/b_${tag}_$rep.json" "$s" <<'PY'
 import csv, json, sys

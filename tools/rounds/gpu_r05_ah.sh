@@ -10,7 +10,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_tuning.py -x -q --timeout 1
 rc=$?; tail -3 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 for i in 1 2; do
   for pf in 1 3; do
-    AMG_MZ_PF=$pf timeout -k 10 300 python -u bench.py --cpu-baseline 0 --general 0 > $O/bench_pf${pf}_$i.json 2> $O/bench_pf${pf}_$i.err
+    AMG_MZ_PF=$pf timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --general 0 > $O/bench_pf${pf}_$i.json 2> $O/bench_pf${pf}_$i.err
     rc=$?; [ $rc -eq 0 ] || { echo "bench pf $pf exit $rc"; exit $rc; }
     python3 -c "import json; d=json.load(open('$O/bench_pf${pf}_$i.json')); fk=d.get('fine_kernels',{}); print('pf $pf', d['value'], d['ms_per_step'], {k: round(v.get('ms',0),3) for k,v in fk.items()} if isinstance(fk,dict) else '')"
   done

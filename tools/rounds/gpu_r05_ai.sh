@@ -13,7 +13,7 @@ AMG_MZ_PF=3 AMG_MZ_HPF=1 timeout -k 10 300 python -u -m pytest tests/test_gpu_tu
 rc=$?; tail -1 $O/tests_h1.log; [ $rc -eq 0 ] || exit $rc
 run() { # tag env...
   local tag=$1; shift
-  env "$@" timeout -k 10 300 python -u bench.py --cpu-baseline 0 --general 0 > $O/bench_$tag.json 2> $O/bench_$tag.err
+  env "$@" timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --general 0 > $O/bench_$tag.json 2> $O/bench_$tag.err
   local rc=$?; [ $rc -eq 0 ] || { echo "bench $tag exit $rc"; exit $rc; }
   python3 -c "import json; d=json.load(open('$O/bench_$tag.json')); fk=d['fine_kernels']; print('$tag', round(d['value'],1), round(d['ms_per_step'],4), {k: round(v['ms'],3) for k,v in fk.items()})"
 }

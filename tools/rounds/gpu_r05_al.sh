@@ -15,10 +15,10 @@ step() { # name timeout cmd...
    echo "$name exit $rc"; tail -c 300 $P/$name.json; echo
    case $rc in 0) ;; *) echo "stopping after $name"; exit $rc;; esac
 }
-step bench 500 python -u bench.py
+step bench 500 python -u bench.py --full
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o run \
-   -- python3 $R/bench.py --steps 10 --warmup 2 --cpu-baseline 0 --general 0 > $P/trace_bench.json 2> $P/trace_bench.err
+   -- python3 $R/bench.py --full --steps 10 --warmup 2 --cpu-baseline 0 --general 0 > $P/trace_bench.json 2> $P/trace_bench.err
 rc=$?; echo "trace exit $rc"; [ $rc -eq 0 ] || exit $rc
 f=$(find $P/trace -name "*kernel_trace.csv" | head -1)
 python3 $R/tools/step_breakdown.py $f > $P/step_breakdown.txt; head -2 $P/step_breakdown.txt; rm -f $f

@@ -11,7 +11,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_tuning.py tests/test_gpu_ma
 rc=$?; echo "tests: $(tail -1 $O/tests.log)"; [ $rc -eq 0 ] || exit $rc
 run() { # tag env...
   local tag=$1; shift
-  env "$@" timeout -k 10 300 python -u bench.py --cpu-baseline 0 --general 0 > $O/bench_$tag.json 2> $O/bench_$tag.err
+  env "$@" timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --general 0 > $O/bench_$tag.json 2> $O/bench_$tag.err
   local rc=$?; [ $rc -eq 0 ] || { echo "bench $tag exit $rc"; exit $rc; }
   python3 -c "import json; d=json.load(open('$O/bench_$tag.json')); s=d['fine_spmv']; print('$tag', round(d['value'],1), 'spmv', round(s['ms'],4), 'ms', round(s['frac'],4))"
 }

@@ -27,11 +27,11 @@ echo "config 3 tile: $(grep -o '"cycles_per_s": [0-9.]*' $O/async3_tile.json | t
 timeout -k 10 400 python -u -m pytest tests/test_gpu_dist.py -k "async_jacobi_512" -m slow -v -s -rf --timeout 380 \
    --timeout-method thread > $O/ajac512.log 2>&1; echo "ajac512 exit $?"; grep -E "512\^3|passed|failed" $O/ajac512.log | tail -6
 for occ in 1 2; do
-  AMG_FUSE_OUTER_OCC=$occ timeout -k 10 200 python -u bench.py --fuse-outer 2 --cpu-baseline 0 --general 0 \
+  AMG_FUSE_OUTER_OCC=$occ timeout -k 10 200 python -u bench.py --full --fuse-outer 2 --cpu-baseline 0 --general 0 \
      > $O/fo2_occ$occ.json 2> $O/fo2_occ$occ.err
   echo "fuse_outer 2 occ $occ exit $?: $(grep -o '"ms_per_step": [0-9.]*' $O/fo2_occ$occ.json)"
 done
-timeout -k 10 200 python -u bench.py --cpu-baseline 0 --general 0 > $O/fo0.json 2> $O/fo0.err
+timeout -k 10 200 python -u bench.py --full --cpu-baseline 0 --general 0 > $O/fo0.json 2> $O/fo0.err
 echo "fuse_outer 0: $(grep -o '"ms_per_step": [0-9.]*' $O/fo0.json)"
 for xs in 1 0; do
   AMG_BSR3_XS=$xs timeout -k 10 300 python -u tools/bench_elasticity.py --refine 5 > $O/elast5_xs$xs.json 2> $O/elast5_xs$xs.err
