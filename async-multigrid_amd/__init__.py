@@ -21,7 +21,7 @@ from .abi import AmgError, AmgOpts  # noqa: F401
 from .abi import (AMG_JACOBI, AMG_GAUSS_SEIDEL, AMG_HYBRID_JGS, AMG_SYMM_JACOBI,  # noqa: F401
                   AMG_L1_JACOBI, AMG_L1_HYBRID_JGS, AMG_MULT, AMG_AFACX, AMG_MULTADD,
                   AMG_ASYNC_AFACX, AMG_ASYNC_MULTADD, AMG_INTERP_LINEAR, AMG_INTERP_AGGREGATE,
-                  AMG_GEN_A, AMG_GEN_P, AMG_GEN_R, AMG_VEC_F, AMG_VEC_U, AMG_VEC_R,
+                  AMG_GEN_A, AMG_GEN_P, AMG_GEN_R, AMG_GEN_PS, AMG_GEN_RS, AMG_VEC_F, AMG_VEC_U, AMG_VEC_R,
                   AMG_ASYNC_GS, AMG_SEMI_ASYNC_GS, AMG_BPX, AMG_NO_ACCEL, AMG_RICHARD_ACCEL,
                   AMG_CHEBY_RECUR_ACCEL, AMG_FULL_ASYNC, AMG_SEMI_ASYNC, AMG_LOCAL, AMG_GLOBAL,
                   AMG_READ_SOL, AMG_READ_RES, AMG_DELAY_NONE, AMG_DELAY_ONE, AMG_DELAY_SOME,

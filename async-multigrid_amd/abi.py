@@ -42,6 +42,7 @@ AMG_NO_ACCEL, AMG_RICHARD_ACCEL, AMG_CHEBY_RECUR_ACCEL = 0, 1, 2
 AMG_VEC_F, AMG_VEC_U, AMG_VEC_R = 0, 1, 2
 AMG_INTERP_LINEAR, AMG_INTERP_AGGREGATE = 0, 1
 AMG_GEN_A, AMG_GEN_P, AMG_GEN_R = 0, 1, 2
+AMG_GEN_PS, AMG_GEN_RS = 3, 4  # classical hierarchies only: smoothed P~ / R~
 
 
 class AmgOpts(C.Structure):
@@ -69,7 +70,8 @@ AMG_SPS_EXPONENTIAL, AMG_SPS_INVERSE, AMG_SPS_RANDOM = 0, 1, 2
 class AmgClassicalOpts(C.Structure):
     _fields_ = [("coarsen_type", _i), ("interp_type", _i), ("strong_threshold", _d),
                 ("max_row_sum", _d), ("max_levels", _i), ("max_coarse_size", _i),
-                ("num_functions", _i), ("seed", C.c_ulonglong), ("device", _i)]
+                ("num_functions", _i), ("seed", C.c_ulonglong), ("device", _i),
+                ("P_max_elmts", _i), ("trunc_factor", _d)]
 
 
 AMG_COARSEN_PMIS, AMG_COARSEN_PMIS_FIXED, AMG_COARSEN_HMIS = 8, 9, 10
@@ -182,6 +184,8 @@ PROTOTYPES = {
     "amg_classical_get": (_i, [_p, _i, _i, _ip, _ip, _llp, C.POINTER(_ip), C.POINTER(_ip),
                                C.POINTER(_dp)]),
     "amg_classical_register": (_i, [_p, _p, _i, _i, _pp]),
+    "amg_classical_smooth_transfers": (_i, [_p, _d, _i, _d, _i]),
+    "amg_csr_truncate": (_i, [_i, _i, _ip, _ip, _dp, _d, _i, _ip, _ip, _dp, _llp]),
     "amg_classical_cf_marker": (_i, [_p, _i, _ip]),
     "amg_classical_free": (_i, [_p]),
     "amg_elast_create": (_i, [_i, _pp]),

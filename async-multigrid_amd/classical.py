@@ -1,14 +1,17 @@
 """In-house classical AMG setup (amg_classical_*): the hierarchy the reference
 gets from HYPRE_BoomerAMGSetup (SMEM_Setup.cpp:55-70, DMEM_Setup.cpp:169-173),
 built on the host by the library -- strength of connection, HMIS / PMIS
-coarsening, extended+i or direct interpolation, Galerkin R A P."""
+coarsening, extended+i or direct interpolation, optional truncation of P
+(P_max_elmts / trunc_factor), Galerkin R A P, and the explicit smoothed
+transfers of MULTADD (smooth_transfers, optionally truncated)."""
 import ctypes as C
 
 import numpy as np
 
 from . import abi
 from .abi import (AMG_CLASSICAL_DIRECT, AMG_CLASSICAL_EXT_I, AMG_COARSEN_HMIS,  # noqa: F401
-                  AMG_COARSEN_PMIS, AMG_COARSEN_PMIS_FIXED, AMG_GEN_A, AMG_GEN_P, AMG_GEN_R)
+                  AMG_COARSEN_PMIS, AMG_COARSEN_PMIS_FIXED, AMG_GEN_A, AMG_GEN_P, AMG_GEN_PS, AMG_GEN_R,
+                  AMG_GEN_RS)
 
 
 def elasticity(refine):
@@ -41,6 +44,25 @@ def default_opts(**kw):
     return o
 
 
+def truncate_rows(n, rowptr, col, val, trunc_factor, max_elmts, device=-1):
+    """amg_csr_truncate: the rows of a CSR truncated by the interpolation
+    truncation rule (include/amg_mi355x.h), on the host (device -1) or on that
+    GPU; numpy (rowptr, col, val)."""
+    from . import check, lib
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    cj = np.ascontiguousarray(col, dtype=np.int32)
+    v = np.ascontiguousarray(val, dtype=np.float64)
+    orp = np.zeros(int(n) + 1, dtype=np.int32)
+    ocj = np.zeros(max(cj.size, 1), dtype=np.int32)
+    ov = np.zeros(max(v.size, 1), dtype=np.float64)
+    nz = C.c_longlong()
+    check(lib.amg_csr_truncate(int(device), int(n), rp.ctypes.data_as(abi._ip), cj.ctypes.data_as(abi._ip),
+                               v.ctypes.data_as(abi._dp), float(trunc_factor), int(max_elmts),
+                               orp.ctypes.data_as(abi._ip), ocj.ctypes.data_as(abi._ip), ov.ctypes.data_as(abi._dp),
+                               C.byref(nz)))
+    return orp, ocj[:nz.value].copy(), ov[:nz.value].copy()
+
+
 class ClassicalAMG:
     """Host hierarchy from a square CSR (diagonal first)."""
 
@@ -58,7 +80,8 @@ class ClassicalAMG:
         self.L = lib.amg_classical_levels(h)
 
     def get(self, which, level):
-        """(nrows, ncols, rowptr, col, val) numpy copies of operator which (AMG_GEN_A/P/R)."""
+        """(nrows, ncols, rowptr, col, val) numpy copies of operator which
+        (AMG_GEN_A/P/R; AMG_GEN_PS/RS after smooth_transfers)."""
         from . import check
         nr, nc, nz = C.c_int(), C.c_int(), C.c_longlong()
         rp, cj, v = abi._ip(), abi._ip(), abi._dp()
@@ -68,6 +91,15 @@ class ClassicalAMG:
         return (n, nc.value, np.ctypeslib.as_array(rp, (n + 1,)).copy(),
                 np.ctypeslib.as_array(cj, (max(z, 1),))[:z].copy() if z else np.zeros(0, np.int32),
                 np.ctypeslib.as_array(v, (max(z, 1),))[:z].copy() if z else np.zeros(0))
+
+    def smooth_transfers(self, w, add_P_max_elmts=0, add_trunc_factor=0.0, device=-1):
+        """amg_classical_smooth_transfers: build (or rebuild) every level's
+        P~ = (I - w D^-1 A) P and R~, truncated when an add_* option is set
+        (R~ is then the transpose of the truncated P~); get / register them as
+        AMG_GEN_PS / AMG_GEN_RS."""
+        from . import check
+        check(self._lib.amg_classical_smooth_transfers(self.h, float(w), int(add_P_max_elmts),
+                                                       float(add_trunc_factor), int(device)))
 
     def cf_marker(self, level):
         from . import check
@@ -82,13 +114,14 @@ class ClassicalAMG:
         check(self._lib.amg_classical_register(ctx.h, self.h, which, level, C.byref(h)))
         return Mat(ctx, h)
 
-    def hierarchy(self, ctx, opts, levels=None):
-        """Register every level on the device and build a Hier (amg_hier_create)."""
+    def hierarchy(self, ctx, opts, levels=None, smoothed=False):
+        """Register every level on the device and build a Hier (amg_hier_create);
+        smoothed: the transfers are P~ / R~ of smooth_transfers (MULTADD)."""
         from . import Hier
         L = self.L if levels is None else levels
         As = [self.register(ctx, AMG_GEN_A, l) for l in range(L)]
-        Ps = [self.register(ctx, AMG_GEN_P, l) for l in range(L - 1)]
-        Rs = [self.register(ctx, AMG_GEN_R, l) for l in range(L - 1)]
+        Ps = [self.register(ctx, AMG_GEN_PS if smoothed else AMG_GEN_P, l) for l in range(L - 1)]
+        Rs = [self.register(ctx, AMG_GEN_RS if smoothed else AMG_GEN_R, l) for l in range(L - 1)]
         return Hier(ctx, As, Ps, Rs, opts)
 
     def free(self):

@@ -16,6 +16,11 @@
 //   Galerkin     A_c = R A P with R = P^T (construct_R_flag, SMEM_Setup.cpp:1405-1419),
 //                Gustavson products accumulated in row-entry order, columns
 //                sorted, diagonal first
+//   truncation   P_max_elmts / trunc_factor (hypre_BoomerAMGInterpTruncation,
+//                restated in truncate_rows) on each level's P before R = P^T
+//   smoothed     P~ = (I - w D^-1 A) P, R~ = P^T (I - w D^-1 A)^T (SmoothTransfer,
+//   transfers    SMEM_Setup.cpp:1173-1254, Jacobi form), optionally truncated
+//                (add_P_max_elmts / add_trunc_factor)
 // Levels are built until the coarse operator has at most max_coarse_size rows,
 // coarsening stalls, or max_levels is reached.
 #include <algorithm>
@@ -41,6 +46,19 @@ int amg_rap_device(int device, int An, const std::vector<int> &arp, const std::v
                    const std::vector<double> &pv, int Pm, int Rn, const std::vector<int> &rrp,
                    const std::vector<int> &rcj, const std::vector<double> &rv, std::vector<int> &crp,
                    std::vector<int> &ccj, std::vector<double> &cv);
+
+// amg_trunc.hip: rows truncated on a GPU, bit-identical to truncate_rows() below
+int amg_truncate_device(int device, int n, const int *rp, const int *cj, const double *v, double tf, int maxel,
+                        std::vector<int> &orp, std::vector<int> &ocj, std::vector<double> &ov);
+// amg_spgemm.hip: one level's SmoothTransfer on a GPU (P~ truncated there when an
+// add_* option is set, R~ then left to the caller), bit-identical to the host's
+int amg_smooth_transfer_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
+                               const std::vector<double> &av, const std::vector<int> &prp,
+                               const std::vector<int> &pcj, const std::vector<double> &pv, int Pm,
+                               const std::vector<int> &rrp, const std::vector<int> &rcj,
+                               const std::vector<double> &rv, double w, int add_max, double add_tf,
+                               std::vector<int> &psrp, std::vector<int> &pscj, std::vector<double> &psv,
+                               std::vector<int> &rsrp, std::vector<int> &rscj, std::vector<double> &rsv);
 
 namespace {
 
@@ -216,6 +234,90 @@ void spgemm(const HCsr &A, const HCsr &B, HCsr &C)
       C.rp[r + 1] = (int)C.cj.size();
    }
    diag_first(C);
+}
+
+// hypre_BoomerAMGInterpTruncation restated, row by row:
+//   threshold pass (trunc_factor > 0): s = the row's sum, m = max |v|; entries
+//     with |v| < trunc_factor m go; k = the kept entries' sum; when k != 0 each
+//     kept value is multiplied by s / k
+//   count pass (max_elmts > 0, row still longer): s = the current sum; the
+//     max_elmts entries first in the order (|v| descending, column ascending,
+//     position ascending) stay, in column order; k and the rescale as above
+// Sums run in storage order.  A pass that drops nothing leaves the row as it is
+// (s and k are then the same sum).  The tie rule is this library's: hypre's
+// follows its quicksort.
+void truncate_rows(int n, const int *rp, const int *mcj, const double *mv, double tf, int maxel, HCsr &T)
+{
+   rows_parallel(n, T, [&](int r0, int r1, std::vector<int> &cnt, std::vector<int> &cj, std::vector<double> &v) {
+      std::vector<int> c, ord;
+      std::vector<double> w;
+      std::vector<char> keep;
+      auto compact = [&](double s) { // kept entries in order, rescaled by s / (their sum)
+         double k = 0.0;
+         size_t q = 0;
+         for (size_t i = 0; i < w.size(); i++)
+            if (keep[i]) {
+               k += w[i];
+               c[q] = c[i];
+               w[q++] = w[i];
+            }
+         if (q == w.size()) return;
+         c.resize(q);
+         w.resize(q);
+         if (k != 0.0) {
+            const double f = s / k;
+            for (double &x : w) x = x * f;
+         }
+      };
+      for (int r = r0; r < r1; r++) {
+         c.assign(mcj + rp[r], mcj + rp[r + 1]);
+         w.assign(mv + rp[r], mv + rp[r + 1]);
+         if (tf > 0.0 && w.size() > 1) {
+            double s = 0.0, m = 0.0;
+            for (double x : w) {
+               s += x;
+               m = std::fmax(m, std::fabs(x));
+            }
+            const double thr = tf * m;
+            keep.assign(w.size(), 1);
+            for (size_t i = 0; i < w.size(); i++)
+               if (std::fabs(w[i]) < thr) keep[i] = 0;
+            compact(s);
+         }
+         if (maxel > 0 && (int)w.size() > maxel) {
+            double s = 0.0;
+            for (double x : w) s += x;
+            ord.resize(w.size());
+            for (size_t i = 0; i < w.size(); i++) ord[i] = (int)i;
+            std::sort(ord.begin(), ord.end(), [&](int a, int b) {
+               const double fa = std::fabs(w[a]), fb = std::fabs(w[b]);
+               if (fa != fb) return fa > fb;
+               if (c[a] != c[b]) return c[a] < c[b];
+               return a < b;
+            });
+            keep.assign(w.size(), 0);
+            for (int i = 0; i < maxel; i++) keep[ord[i]] = 1;
+            compact(s);
+         }
+         cj.insert(cj.end(), c.begin(), c.end());
+         v.insert(v.end(), w.begin(), w.end());
+         cnt[r] = (int)c.size();
+      }
+   });
+}
+
+// M's rows truncated in place, on the host or on GPU `device`
+int truncate_csr(HCsr &M, double tf, int maxel, int device)
+{
+   HCsr T;
+   T.n = M.n;
+   T.m = M.m;
+   if (device >= 0)
+      AMG_TRY(amg_truncate_device(device, M.n, M.rp.data(), M.cj.data(), M.v.data(), tf, maxel, T.rp, T.cj, T.v));
+   else
+      truncate_rows(M.n, M.rp.data(), M.cj.data(), M.v.data(), tf, maxel, T);
+   M = std::move(T);
+   return AMG_OK;
 }
 
 uint64_t splitmix64(uint64_t x)
@@ -459,6 +561,7 @@ void interpolation(const HCsr &A, const HCsr &S, const std::vector<int> &cf, int
 
 struct amg_classical {
    std::vector<HCsr> A, P, R;
+   std::vector<HCsr> PS, RS; // smoothed transfers (amg_classical_smooth_transfers)
    std::vector<std::vector<int>> cf;
 };
 
@@ -474,6 +577,8 @@ extern "C" void amg_classical_opts_default(amg_classical_opts *o)
    o->num_functions = 1;
    o->seed = 2747;
    o->device = -1;
+   o->P_max_elmts = 0; // hypre's default (no -P_max_elmts): P as interpolation() leaves it
+   o->trunc_factor = 0.0;
 }
 
 extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int *rowptr, const int *col,
@@ -488,6 +593,9 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
    AMG_ARG(o->num_functions >= 1 && n % o->num_functions == 0, "amg_classical_setup: num_functions %d",
            o->num_functions);
    AMG_ARG(o->max_levels >= 1, "amg_classical_setup: max_levels %d", o->max_levels);
+   AMG_ARG(o->P_max_elmts >= 0 && o->trunc_factor >= 0.0 && o->trunc_factor <= 1.0,
+           "amg_classical_setup: P_max_elmts %d, trunc_factor %g (>= 0, trunc_factor <= 1)", o->P_max_elmts,
+           o->trunc_factor);
    const long long nnz = rowptr[n];
    AMG_ARG(rowptr[0] == 0 && nnz >= 0, "amg_classical_setup: rowptr");
    auto *H = new amg_classical();
@@ -525,6 +633,13 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
       interpolation(A, S, cf, o->interp_type, nfun, P, &nc);
       auto t3 = now();
       if (nc == 0 || nc == A.n) break; // coarsening stalled
+      if (o->P_max_elmts > 0 || o->trunc_factor > 0.0) {
+         const int st = truncate_csr(P, o->trunc_factor, o->P_max_elmts, o->device);
+         if (st != AMG_OK) {
+            delete H;
+            return st;
+         }
+      }
       HCsr R, AP, Ac;
       transpose(P, R);
       if (o->device >= 0) {
@@ -559,8 +674,12 @@ extern "C" int amg_classical_levels(const amg_classical *H) { return H ? (int)H-
 static const HCsr *pick(const amg_classical *H, int which, int level)
 {
    if (!H || level < 0) return nullptr;
-   const auto &v = which == AMG_GEN_A ? H->A : which == AMG_GEN_P ? H->P : which == AMG_GEN_R ? H->R : H->A;
-   if (which != AMG_GEN_A && which != AMG_GEN_P && which != AMG_GEN_R) return nullptr;
+   if (which < AMG_GEN_A || which > AMG_GEN_RS) return nullptr;
+   const auto &v = which == AMG_GEN_A    ? H->A
+                   : which == AMG_GEN_P  ? H->P
+                   : which == AMG_GEN_R  ? H->R
+                   : which == AMG_GEN_PS ? H->PS
+                                         : H->RS;
    return level < (int)v.size() ? &v[level] : nullptr;
 }
 
@@ -585,6 +704,70 @@ extern "C" int amg_classical_register(amg_ctx *ctx, const amg_classical *H, int 
    AMG_ARG(ctx && out && M, "amg_classical_register: no operator %d on level %d", which, level);
    return amg_csr_register(ctx, M->n, M->m, M->nnz(), M->rp.data(), M->cj.data(), M->v.data(),
                            which == AMG_GEN_A ? 1 : 0, out);
+}
+
+extern "C" int amg_classical_smooth_transfers(amg_classical *H, double w, int add_P_max_elmts,
+                                              double add_trunc_factor, int device)
+{
+   AMG_ARG(H, "amg_classical_smooth_transfers: no hierarchy");
+   AMG_ARG(add_P_max_elmts >= 0 && add_trunc_factor >= 0.0 && add_trunc_factor <= 1.0,
+           "amg_classical_smooth_transfers: add_P_max_elmts %d, add_trunc_factor %g (>= 0, add_trunc_factor <= 1)",
+           add_P_max_elmts, add_trunc_factor);
+   const bool trunc = add_P_max_elmts > 0 || add_trunc_factor > 0.0;
+   std::vector<HCsr> PS(H->P.size()), RS(H->P.size());
+   for (size_t l = 0; l < H->P.size(); l++) {
+      const HCsr &A = H->A[l], &P = H->P[l], &R = H->R[l];
+      for (int i = 0; i < A.n; i++)
+         AMG_ARG(A.rp[i + 1] > A.rp[i] && A.cj[A.rp[i]] == i,
+                 "amg_classical_smooth_transfers: level %d row %d has no leading diagonal", (int)l, i);
+      HCsr &Ps = PS[l], &Rs = RS[l];
+      Ps.n = P.n, Ps.m = P.m, Rs.n = R.n, Rs.m = R.m;
+      if (device >= 0) {
+         AMG_TRY(amg_smooth_transfer_device(device, A.n, A.rp, A.cj, A.v, P.rp, P.cj, P.v, P.m, R.rp, R.cj, R.v, w,
+                                            add_P_max_elmts, add_trunc_factor, Ps.rp, Ps.cj, Ps.v, Rs.rp, Rs.cj,
+                                            Rs.v));
+      } else {
+         // or_smooth_transfer's arithmetic: G = I - w D^-1 A on A's pattern
+         HCsr G = A;
+         for (int i = 0; i < A.n; i++) {
+            G.v[A.rp[i]] = 1.0 - w;
+            for (int k = A.rp[i] + 1; k < A.rp[i + 1]; k++) G.v[k] = -w * A.v[k] / A.v[A.rp[i]];
+         }
+         spgemm(G, P, Ps);
+         if (trunc) {
+            AMG_TRY(truncate_csr(Ps, add_trunc_factor, add_P_max_elmts, -1));
+         } else {
+            for (int i = 0; i < A.n; i++)
+               for (int k = A.rp[i] + 1; k < A.rp[i + 1]; k++) G.v[k] = -w * A.v[k] / A.v[A.rp[A.cj[k]]];
+            spgemm(R, G, Rs);
+         }
+      }
+      if (trunc) transpose(Ps, Rs); // R~ = (truncated P~)^T, values copied: the preconditioner stays symmetric
+   }
+   H->PS = std::move(PS);
+   H->RS = std::move(RS);
+   return AMG_OK;
+}
+
+extern "C" int amg_csr_truncate(int device, int n, const int *rowptr, const int *col, const double *val,
+                                double trunc_factor, int max_elmts, int *out_rowptr, int *out_col, double *out_val,
+                                long long *out_nnz)
+{
+   AMG_ARG(n > 0 && rowptr && out_rowptr && out_nnz && rowptr[0] == 0, "amg_csr_truncate: bad argument");
+   AMG_ARG(max_elmts >= 0 && trunc_factor >= 0.0 && trunc_factor <= 1.0,
+           "amg_csr_truncate: max_elmts %d, trunc_factor %g (>= 0, trunc_factor <= 1)", max_elmts, trunc_factor);
+   for (int i = 0; i < n; i++) AMG_ARG(rowptr[i + 1] >= rowptr[i], "amg_csr_truncate: rowptr decreases at row %d", i);
+   AMG_ARG(rowptr[n] == 0 || (col && val && out_col && out_val), "amg_csr_truncate: bad argument");
+   HCsr T;
+   if (device >= 0)
+      AMG_TRY(amg_truncate_device(device, n, rowptr, col, val, trunc_factor, max_elmts, T.rp, T.cj, T.v));
+   else
+      truncate_rows(n, rowptr, col, val, trunc_factor, max_elmts, T);
+   std::copy(T.rp.begin(), T.rp.end(), out_rowptr);
+   std::copy(T.cj.begin(), T.cj.end(), out_col);
+   std::copy(T.v.begin(), T.v.end(), out_val);
+   *out_nnz = T.nnz();
+   return AMG_OK;
 }
 
 extern "C" int amg_classical_cf_marker(const amg_classical *H, int level, int *cf)

@@ -339,3 +339,100 @@ int amg_rap_device(int device, int An, const std::vector<int> &arp, const std::v
    hipStreamDestroy(s);
    return st;
 }
+
+int amg_trunc_dev(hipStream_t s, int n, const int *d_rp, const int *d_cj, const double *d_v, long long nnz, double tf,
+                  int maxel, int **d_orp, int **d_ocj, double **d_ov, long long *onnz); // amg_trunc.hip
+
+namespace {
+
+// SmoothTransfer's Jacobi factors on A's pattern (A diagonal first), one
+// wavefront per row: g = I - w D^-1 A (first entry 1 - w, else (-w a_ij) / a_ii)
+// and gt, its transpose's values (else (-w a_ij) / a_jj)
+__global__ __launch_bounds__(256) void smooth_factor_k(const int *__restrict__ arp, const int *__restrict__ acj,
+                                                       const double *__restrict__ av, int n, double w,
+                                                       double *__restrict__ g, double *__restrict__ gt)
+{
+   const int lane = threadIdx.x & 63;
+   const int wpb = blockDim.x >> 6;
+   for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n; r += gridDim.x * wpb) {
+      const int b = arp[r], e = arp[r + 1];
+      if (b == e) continue;
+      const double d = av[b];
+      for (int k = b + lane; k < e; k += 64) {
+         if (k == b) {
+            g[k] = gt[k] = 1.0 - w;
+         } else {
+            g[k] = -w * av[k] / d;
+            gt[k] = -w * av[k] / av[arp[acj[k]]];
+         }
+      }
+   }
+}
+
+} // namespace
+
+// SmoothTransfer (Jacobi) of one level on device `device`: P~ = G P and, with
+// the add_* options off, R~ = P^T GT by spgemm_dev (bit-identical to the host
+// products); with one of them on, P~ is truncated on the device before it is
+// downloaded and R~ is left to the caller (the transpose of the truncated P~).
+// R is P^T (host CSR).
+int amg_smooth_transfer_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
+                               const std::vector<double> &av, const std::vector<int> &prp,
+                               const std::vector<int> &pcj, const std::vector<double> &pv, int Pm,
+                               const std::vector<int> &rrp, const std::vector<int> &rcj,
+                               const std::vector<double> &rv, double w, int add_max, double add_tf,
+                               std::vector<int> &psrp, std::vector<int> &pscj, std::vector<double> &psv,
+                               std::vector<int> &rsrp, std::vector<int> &rscj, std::vector<double> &rsv)
+{
+   AMG_HIP(hipSetDevice(device));
+   hipStream_t s;
+   AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+   int *d_arp = nullptr, *d_acj = nullptr, *d_prp = nullptr, *d_pcj = nullptr, *d_rrp = nullptr, *d_rcj = nullptr;
+   int *d_psrp = nullptr, *d_pscj = nullptr, *d_trp = nullptr, *d_tcj = nullptr, *d_rsrp = nullptr, *d_rscj = nullptr;
+   double *d_av = nullptr, *d_g = nullptr, *d_gt = nullptr, *d_pv = nullptr, *d_rv = nullptr, *d_psv = nullptr,
+          *d_tv = nullptr, *d_rsv = nullptr;
+   const bool trunc = add_max > 0 || add_tf > 0.0;
+   auto run = [&]() -> int {
+      AMG_TRY(dupload(s, arp, &d_arp));
+      AMG_TRY(dupload(s, acj, &d_acj));
+      AMG_TRY(dupload(s, av, &d_av));
+      AMG_TRY(dupload(s, prp, &d_prp));
+      AMG_TRY(dupload(s, pcj, &d_pcj));
+      AMG_TRY(dupload(s, pv, &d_pv));
+      AMG_HIP(hipMalloc(&d_g, std::max<size_t>(av.size(), 1) * sizeof(double)));
+      AMG_HIP(hipMalloc(&d_gt, std::max<size_t>(av.size(), 1) * sizeof(double)));
+      smooth_factor_k<<<std::min((An + 3) / 4, 8192), 256, 0, s>>>(d_arp, d_acj, d_av, An, w, d_g, d_gt);
+      AMG_HIP(hipGetLastError());
+      long long psnz = 0, rsnz = 0;
+      AMG_TRY(spgemm_dev(s, An, d_arp, d_acj, d_g, d_prp, d_pcj, d_pv, Pm, &d_psrp, &d_pscj, &d_psv, &psnz));
+      if (trunc) {
+         long long tnz = 0;
+         AMG_TRY(amg_trunc_dev(s, An, d_psrp, d_pscj, d_psv, psnz, add_tf, add_max, &d_trp, &d_tcj, &d_tv, &tnz));
+         AMG_TRY(download(s, d_trp, (size_t)An + 1, psrp));
+         AMG_TRY(download(s, d_tcj, (size_t)tnz, pscj));
+         AMG_TRY(download(s, d_tv, (size_t)tnz, psv));
+      } else {
+         AMG_TRY(download(s, d_psrp, (size_t)An + 1, psrp));
+         AMG_TRY(download(s, d_pscj, (size_t)psnz, pscj));
+         AMG_TRY(download(s, d_psv, (size_t)psnz, psv));
+         AMG_TRY(dupload(s, rrp, &d_rrp));
+         AMG_TRY(dupload(s, rcj, &d_rcj));
+         AMG_TRY(dupload(s, rv, &d_rv));
+         AMG_TRY(spgemm_dev(s, Pm, d_rrp, d_rcj, d_rv, d_arp, d_acj, d_gt, An, &d_rsrp, &d_rscj, &d_rsv, &rsnz));
+         AMG_TRY(download(s, d_rsrp, (size_t)Pm + 1, rsrp));
+         AMG_TRY(download(s, d_rscj, (size_t)rsnz, rscj));
+         AMG_TRY(download(s, d_rsv, (size_t)rsnz, rsv));
+      }
+      AMG_HIP(hipStreamSynchronize(s));
+      return AMG_OK;
+   };
+   const int st = run();
+   hipStreamSynchronize(s);
+   for (void *p : {(void *)d_arp, (void *)d_acj, (void *)d_prp, (void *)d_pcj, (void *)d_rrp, (void *)d_rcj,
+                   (void *)d_psrp, (void *)d_pscj, (void *)d_trp, (void *)d_tcj, (void *)d_rsrp, (void *)d_rscj,
+                   (void *)d_av, (void *)d_g, (void *)d_gt, (void *)d_pv, (void *)d_rv, (void *)d_psv, (void *)d_tv,
+                   (void *)d_rsv})
+      hipFree(p);
+   hipStreamDestroy(s);
+   return st;
+}

@@ -566,12 +566,52 @@ typedef struct {
    int device;              /* >= 0: the Galerkin products A P and R (A P) run on this
                                GPU (amg_spgemm.hip: one lane per row, the host's
                                Gustavson order -- bit-identical); -1: on the host */
+   int P_max_elmts;         /* -P_max_elmts (DMEM_Main.cpp:49,519-523, DMEM_Setup.cpp:541,
+                               SMEM_Setup.cpp:1686): at most this many entries per row of
+                               P; 0 (the reference's default): no limit             */
+   double trunc_factor;     /* hypre's interpolation truncation factor in [0, 1]: entries
+                               below trunc_factor x the row's largest go; 0: none.  With
+                               either set each level's P is truncated (amg_csr_truncate's
+                               rule) before R = P^T and the Galerkin product, on `device`
+                               when that is >= 0 (amg_trunc.hip, bit-identical)      */
 } amg_classical_opts;
 void amg_classical_opts_default(amg_classical_opts *o); /* the SMEM parameters */
 int amg_classical_setup(const amg_classical_opts *o, int n, const int *rowptr, const int *col,
                         const double *val, amg_classical **out);
 int amg_classical_levels(const amg_classical *h);
-/* operator which (AMG_GEN_A/P/R) of a level: sizes and pointers into h */
+/* explicit smoothed transfers of MULTADD / ASYNC_MULTADD for every level l < L-1
+ * (SmoothTransfer, SMEM_Setup.cpp:1173-1254, Jacobi form): with G = I - w D^-1 A_l
+ * (diagonal 1 - w, off-diagonal (-w a_ij) / a_ii) P~ = G P_l and R~ = P_l^T G^T
+ * (off-diagonal (-w a_ij) / a_jj), Gustavson products in the library's order with
+ * sorted columns, on the host (device -1) or on that GPU (bit-identical).
+ * add_P_max_elmts / add_trunc_factor (-add_P_max_elmts, -add_trunc_factor:
+ * DMEM_Main.cpp:50-51,524-531, DMEM_Setup.cpp:573,591-592): when either is
+ * non-zero P~ is truncated by amg_csr_truncate's rule (on the device before it
+ * is downloaded) and R~ is the exact transpose of the truncated P~, values
+ * copied, as in hypre's mult-additive setup: the additive preconditioner stays
+ * symmetric, and R~ then no longer equals the separately rounded product
+ * P^T G^T.  A repeated call replaces the stored P~ / R~. */
+#define AMG_GEN_PS 3 /* smoothed P~ of a level (after amg_classical_smooth_transfers) */
+#define AMG_GEN_RS 4 /* smoothed R~ */
+int amg_classical_smooth_transfers(amg_classical *h, double smooth_weight, int add_P_max_elmts,
+                                   double add_trunc_factor, int device);
+/* rows of a host CSR truncated; device >= 0: on that GPU, -1: host (bit-identical).
+ * hypre_BoomerAMGInterpTruncation restated (hypre is not in the reference tree:
+ * parity unpinned).  Per row, sums in storage order:
+ *   1. trunc_factor > 0: s = the row's sum, m = max |v|; entries with
+ *      |v| < trunc_factor m are dropped; k = the kept sum; if k != 0 every kept
+ *      value is multiplied by s / k;
+ *   2. max_elmts > 0 and more than max_elmts entries left: s = the current sum;
+ *      the max_elmts entries of largest |v| stay (ties: the smaller column -- this
+ *      library's rule, hypre's follows its quicksort), in column order; k and the
+ *      rescale as in 1.
+ * A pass that drops nothing leaves the row bit-identical.  out_* are
+ * caller-allocated at the input's sizes; *out_nnz <= nnz.  trunc_factor outside
+ * [0, 1] or max_elmts < 0: AMG_ERR_ARG. */
+int amg_csr_truncate(int device, int n, const int *rowptr, const int *col, const double *val,
+                     double trunc_factor, int max_elmts, int *out_rowptr, int *out_col,
+                     double *out_val, long long *out_nnz);
+/* operator which (AMG_GEN_A/P/R, AMG_GEN_PS/RS) of a level: sizes and pointers into h */
 int amg_classical_get(const amg_classical *h, int which, int level, int *nrows, int *ncols,
                       long long *nnz, const int **rowptr, const int **col, const double **val);
 /* register it on the device (amg_csr_register) */

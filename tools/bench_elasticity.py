@@ -2,7 +2,9 @@
 refined r times, Q1 byVDIM) on the in-house classical hierarchy
 (num_functions = 3, PMIS fixed seed, extended+i, theta 0.5: the DMEM
 parameters), SMEM_Solve MULT V(1,1) weighted Jacobi.  Prints one JSON line:
-V-cycle iterations/s, fine SpMV time and its bytes in the stored format."""
+V-cycle iterations/s, fine SpMV time and its bytes in the stored format, and
+per level the rows and entries per row.  --P-max-elmts / --trunc-factor build
+the hierarchy with truncated interpolation (the reference's -P_max_elmts)."""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +28,8 @@ def main():
     p.add_argument("--theta", type=float, default=0.5)
     p.add_argument("--omega", type=float, default=0.6)
     p.add_argument("--gpu-setup", type=int, default=1, help="Galerkin products on the GPU (classical opts.device)")
+    p.add_argument("--P-max-elmts", type=int, default=0, help="classical opts.P_max_elmts (0: no truncation)")
+    p.add_argument("--trunc-factor", type=float, default=0.0, help="classical opts.trunc_factor (0: none)")
     p.add_argument("--async-ranks", type=int, default=0,
                    help="also run config 5's asynchronous additive cycle (DMEM_Add: ASYNC_MULTADD, smoothed "
                         "transfers composed) on this hierarchy as R row-partitioned ranks (threads on this GPU)")
@@ -38,7 +42,8 @@ def main():
     n, rp, cj, v, b = amg.classical.elasticity(a.refine)
     t1 = time.time()
     H = amg.classical.ClassicalAMG(n, rp, cj, v, coarsen_type=a.coarsen, strong_threshold=a.theta,
-                                   num_functions=3, device=0 if a.gpu_setup else -1)
+                                   num_functions=3, device=0 if a.gpu_setup else -1,
+                                   P_max_elmts=a.P_max_elmts, trunc_factor=a.trunc_factor)
     t2 = time.time()
     print(f"[elast] r={a.refine}: {n} dofs, {len(cj)} nnz; generated {t1 - t0:.1f}s, classical setup "
           f"{t2 - t1:.1f}s, {H.L} levels", file=sys.stderr, flush=True)
@@ -48,6 +53,9 @@ def main():
     As = Hd._keep[0]
     sizes = [m.nrows for m in As]
     opc = sum(m.nnz for m in As) / As[0].nnz
+    per_level = [{"level": l, "rows": int(m.nrows), "nnz": int(m.nnz), "per_row": m.nnz / m.nrows,
+                  "P_per_row": (Hd._keep[1][l].nnz / Hd._keep[1][l].nrows) if l < len(As) - 1 else None}
+                 for l, m in enumerate(As)]
     fv = ctx.vec(b)
     r0 = Hd.solve_start(fv, ctx.vec(n))
     Hd.iterate(a.warmup)
@@ -104,7 +112,8 @@ def main():
                        f"SMEM_Solve MULT V(1,1) Jacobi w={a.omega}",
            "it_per_s": a.steps / (t4 - t3), "ms_per_step": (t4 - t3) * 1e3 / a.steps,
            "dofs": n, "nnz_A0": int(A0.nnz), "levels": len(sizes), "level_rows": sizes,
-           "operator_complexity": opc, "matrix_format": fmt,
+           "operator_complexity": opc, "P_max_elmts": a.P_max_elmts, "trunc_factor": a.trunc_factor,
+           "per_level": per_level, "matrix_format": fmt,
            "fine_spmv": {"ms": ms.value, "bytes": spmv_bytes, "gbs": spmv_bytes / (ms.value * 1e-3) / 1e9,
                          "frac": spmv_bytes / (ms.value * 1e-3) / 1e9 / HBM_PEAK_GBS},
            "fine_spmv_csr": {"ms": ms_csr.value, "bytes": csr_bytes,
