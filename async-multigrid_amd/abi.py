@@ -268,6 +268,8 @@ PROTOTYPES.update({
     "amg_triplet_write": (_i, [C.c_char_p, _i, _i, _ip, _ip, _dp, _i]),
     "amg_triplet_text_to_bin": (_i, [C.c_char_p, C.c_char_p]),
     "amg_host_csr_free": (None, [C.POINTER(AmgHostCsr)]),
+    "amg_csr_spgemm": (_i, [_i, _i, _i, _ip, _ip, _dp, _i, _ip, _ip, _dp, C.POINTER(AmgHostCsr)]),
+    "amg_set_spgemm_scratch": (_i, [_ll]),
 })
 
 

@@ -63,6 +63,44 @@ def truncate_rows(n, rowptr, col, val, trunc_factor, max_elmts, device=-1):
     return orp, ocj[:nz.value].copy(), ov[:nz.value].copy()
 
 
+def spgemm(A, B, device=-1):
+    """amg_csr_spgemm: C = A B by the setup's rule (Gustavson order, sorted
+    columns, diagonal first when C is square), on the host (device -1) or on
+    that GPU; A, B and C are (nrows, ncols, rowptr, col, val) like
+    ClassicalAMG.get."""
+    from . import check, lib
+    an, am, arp, acj, av = A
+    bn, bm, brp, bcj, bv = B
+    if int(am) != int(bn):
+        raise ValueError(f"spgemm: A has {am} columns, B has {bn} rows")
+    arp, brp = (np.ascontiguousarray(x, dtype=np.int32) for x in (arp, brp))
+    acj, bcj = (np.ascontiguousarray(x, dtype=np.int32) for x in (acj, bcj))
+    av, bv = (np.ascontiguousarray(x, dtype=np.float64) for x in (av, bv))
+    if arp.size != int(an) + 1 or brp.size != int(bn) + 1:
+        raise ValueError("spgemm: rowptr length")
+    if acj.size != av.size or bcj.size != bv.size or acj.size < arp[-1] or bcj.size < brp[-1]:
+        raise ValueError("spgemm: col / val length")
+    h = abi.AmgHostCsr()
+    check(lib.amg_csr_spgemm(int(device), int(an), int(am), arp.ctypes.data_as(abi._ip),
+                             acj.ctypes.data_as(abi._ip), av.ctypes.data_as(abi._dp), int(bm),
+                             brp.ctypes.data_as(abi._ip), bcj.ctypes.data_as(abi._ip), bv.ctypes.data_as(abi._dp),
+                             C.byref(h)))
+    try:
+        n, z = h.nrows, h.nnz
+        return (n, h.ncols, np.ctypeslib.as_array(h.rowptr, (n + 1,)).copy(),
+                np.ctypeslib.as_array(h.col, (z,)).copy() if z else np.zeros(0, np.int32),
+                np.ctypeslib.as_array(h.val, (z,)).copy() if z else np.zeros(0))
+    finally:
+        lib.amg_host_csr_free(C.byref(h))
+
+
+def set_spgemm_scratch(slots):
+    """amg_set_spgemm_scratch: the device product's scratch budget in table
+    slots per batch of rows, process-wide; 0 restores the default."""
+    from . import check, lib
+    check(lib.amg_set_spgemm_scratch(int(slots)))
+
+
 class ClassicalAMG:
     """Host hierarchy from a square CSR (diagonal first)."""
 

@@ -770,6 +770,56 @@ extern "C" int amg_csr_truncate(int device, int n, const int *rowptr, const int 
    return AMG_OK;
 }
 
+// rowptr / col of an n x m CSR as the callers of spgemm() need them
+static int check_csr(const char *who, int n, int m, const int *rp, const int *cj, const double *v)
+{
+   AMG_ARG(rp && rp[0] == 0, "amg_csr_spgemm: %s: rowptr", who);
+   for (int i = 0; i < n; i++) AMG_ARG(rp[i + 1] >= rp[i], "amg_csr_spgemm: %s: rowptr decreases at row %d", who, i);
+   AMG_ARG(rp[n] == 0 || (cj && v), "amg_csr_spgemm: %s: bad argument", who);
+   for (int k = 0; k < rp[n]; k++)
+      AMG_ARG(cj[k] >= 0 && cj[k] < m, "amg_csr_spgemm: %s: column %d outside [0, %d)", who, cj[k], m);
+   return AMG_OK;
+}
+
+extern "C" int amg_csr_spgemm(int device, int An, int Am, const int *arp, const int *acj, const double *av, int Bm,
+                              const int *brp, const int *bcj, const double *bv, amg_host_csr *out)
+{
+   AMG_ARG(out && An > 0 && Am > 0 && Bm > 0, "amg_csr_spgemm: bad argument");
+   *out = amg_host_csr{};
+   AMG_TRY(check_csr("A", An, Am, arp, acj, av));
+   AMG_TRY(check_csr("B", Am, Bm, brp, bcj, bv));
+   HCsr A, B, Cm;
+   A.n = An, A.m = Am;
+   A.rp.assign(arp, arp + An + 1);
+   A.cj.assign(acj, acj + arp[An]);
+   A.v.assign(av, av + arp[An]);
+   B.n = Am, B.m = Bm;
+   B.rp.assign(brp, brp + Am + 1);
+   B.cj.assign(bcj, bcj + brp[Am]);
+   B.v.assign(bv, bv + brp[Am]);
+   if (device >= 0) {
+      Cm.n = An, Cm.m = Bm;
+      AMG_TRY(amg_spgemm_device(device, An, A.rp, A.cj, A.v, Am, B.rp, B.cj, B.v, Bm, Cm.rp, Cm.cj, Cm.v));
+   } else {
+      spgemm(A, B, Cm);
+   }
+   const size_t nz = Cm.cj.size();
+   out->rowptr = (int *)std::malloc(sizeof(int) * ((size_t)An + 1));
+   out->col = (int *)std::malloc(sizeof(int) * std::max<size_t>(nz, 1));
+   out->val = (double *)std::malloc(sizeof(double) * std::max<size_t>(nz, 1));
+   if (!out->rowptr || !out->col || !out->val) {
+      amg_host_csr_free(out);
+      return amg_set_error(AMG_ERR_OOM, "amg_csr_spgemm: out of host memory");
+   }
+   std::copy(Cm.rp.begin(), Cm.rp.end(), out->rowptr);
+   std::copy(Cm.cj.begin(), Cm.cj.end(), out->col);
+   std::copy(Cm.v.begin(), Cm.v.end(), out->val);
+   out->nrows = An;
+   out->ncols = Bm;
+   out->nnz = (long long)nz;
+   return AMG_OK;
+}
+
 extern "C" int amg_classical_cf_marker(const amg_classical *H, int level, int *cf)
 {
    AMG_ARG(H && cf && level >= 0 && level < (int)H->cf.size(), "amg_classical_cf_marker: bad level");

@@ -14,12 +14,17 @@
 // run in batches sized to a scratch budget (upper bound per row: the sum of
 // the B rows its A entries name).
 #include <algorithm>
+#include <atomic>
 #include <numeric>
 #include <vector>
 
 #include "amg_internal.h"
 
 namespace {
+
+// scratch budget of one batch of spgemm_dev, in table slots (amg_set_spgemm_scratch)
+constexpr long long SPGEMM_BUDGET = 1LL << 29;
+std::atomic<long long> g_budget{SPGEMM_BUDGET};
 
 // ub[r] = sum of |B row k| over the entries (r, k) of A
 __global__ void spgemm_ub_k(const int *__restrict__ arp, const int *__restrict__ acj, const int *__restrict__ brp,
@@ -156,7 +161,7 @@ int spgemm_dev(hipStream_t s, int An, const int *d_arp, const int *d_acj, const 
          capr[r] = c;
       }
       // batches of rows within the scratch budget (12 bytes per slot)
-      const long long budget = 1LL << 29; // slots: 6 GiB of scratch
+      const long long budget = g_budget.load(); // slots: 6 GiB of scratch by default
       long long maxb = 1;
       for (int r0 = 0; r0 < An;) {
          long long tot = 0;
@@ -253,6 +258,13 @@ int download(hipStream_t s, const T *d, size_t n, std::vector<T> &h)
 }
 
 } // namespace
+
+extern "C" int amg_set_spgemm_scratch(long long slots)
+{
+   AMG_ARG(slots >= 0, "amg_set_spgemm_scratch: %lld slots", slots);
+   g_budget.store(slots ? slots : SPGEMM_BUDGET);
+   return AMG_OK;
+}
 
 // C = A B on device `device` (host CSR in and out; bit-identical to the host
 // Gustavson spgemm).  An x Am, B Am x Bm.

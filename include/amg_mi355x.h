@@ -906,6 +906,27 @@ int amg_triplet_write(const char *path, int nrows, int ncols, const int *rowptr,
 int amg_triplet_text_to_bin(const char *in_path, const char *out_path);
 void amg_host_csr_free(amg_host_csr *M);
 
+/* ---- the classical setup's sparse product, on its own --------------------------- */
+/* C = A B by the library's rule (the Galerkin products and the smoothed transfers
+ * of amg_classical_* are built from it): A An x Am, B Am x Bm, host CSR.  Each row
+ * of C is accumulated in Gustavson order -- the products of the row's (A entry,
+ * B entry) pairs in storage order, a column's first contribution added to 0.0, a
+ * repeated column added again, a sum that cancels kept as a stored 0.0 -- with
+ * the columns sorted ascending and, when C is square (An == Bm), the diagonal
+ * moved first in the rows that have one.  device >= 0: on that GPU
+ * (amg_spgemm.hip), -1: on the host (bit-identical).  C comes back in *out: release
+ * it with amg_host_csr_free.  An, Am or Bm <= 0, rowptr[0] != 0, a decreasing
+ * rowptr or a column outside [0, Am) / [0, Bm): AMG_ERR_ARG, before anything is
+ * launched. */
+int amg_csr_spgemm(int device, int An, int Am, const int *arp, const int *acj, const double *av,
+                   int Bm, const int *brp, const int *bcj, const double *bv, amg_host_csr *out);
+/* scratch budget of the device product, process-wide: rows of C are computed in
+ * batches whose hash tables (per row the smallest power of two >= twice the
+ * row's product count, >= 2 slots, 12 bytes a slot) fit in `slots`; a row whose
+ * table alone is larger is a batch of its own.  0: the default, 1 << 29.  The
+ * result does not depend on it.  slots < 0: AMG_ERR_ARG. */
+int amg_set_spgemm_scratch(long long slots);
+
 #ifdef __cplusplus
 }
 #endif
