@@ -71,7 +71,7 @@ class AmgClassicalOpts(C.Structure):
     _fields_ = [("coarsen_type", _i), ("interp_type", _i), ("strong_threshold", _d),
                 ("max_row_sum", _d), ("max_levels", _i), ("max_coarse_size", _i),
                 ("num_functions", _i), ("seed", C.c_ulonglong), ("device", _i),
-                ("P_max_elmts", _i), ("trunc_factor", _d)]
+                ("P_max_elmts", _i), ("trunc_factor", _d), ("setup_on_device", _i)]
 
 
 AMG_COARSEN_PMIS, AMG_COARSEN_PMIS_FIXED, AMG_COARSEN_HMIS = 8, 9, 10
@@ -270,6 +270,11 @@ PROTOTYPES.update({
     "amg_host_csr_free": (None, [C.POINTER(AmgHostCsr)]),
     "amg_csr_spgemm": (_i, [_i, _i, _i, _ip, _ip, _dp, _i, _ip, _ip, _dp, C.POINTER(AmgHostCsr)]),
     "amg_set_spgemm_scratch": (_i, [_ll]),
+    "amg_csr_strength": (_i, [_i, _i, _ip, _ip, _dp, _d, _d, _i, C.POINTER(AmgHostCsr)]),
+    "amg_csr_transpose": (_i, [_i, _i, _i, _ip, _ip, _dp, C.POINTER(AmgHostCsr)]),
+    "amg_cf_pmis": (_i, [_i, _i, _ip, _ip, C.c_ulonglong, _ip]),
+    "amg_classical_interp": (_i, [_i, _i, _ip, _ip, _dp, _ip, _ip, _ip, _i, _i, C.POINTER(AmgHostCsr)]),
+    "amg_set_setup_scratch": (_i, [_ll]),
 })
 
 

@@ -1,9 +1,12 @@
 """In-house classical AMG setup (amg_classical_*): the hierarchy the reference
 gets from HYPRE_BoomerAMGSetup (SMEM_Setup.cpp:55-70, DMEM_Setup.cpp:169-173),
-built on the host by the library -- strength of connection, HMIS / PMIS
-coarsening, extended+i or direct interpolation, optional truncation of P
-(P_max_elmts / trunc_factor), Galerkin R A P, and the explicit smoothed
-transfers of MULTADD (smooth_transfers, optionally truncated)."""
+built by the library -- strength of connection, HMIS / PMIS coarsening,
+extended+i or direct interpolation, optional truncation of P (P_max_elmts /
+trunc_factor), Galerkin R A P, and the explicit smoothed transfers of MULTADD
+(smooth_transfers, optionally truncated).  On the host by default; device=d moves
+the products and the truncation to that GPU, setup_on_device=1 the whole level
+loop (HMIS still coarsens on the host), bit-identical either way.  strength,
+transpose, pmis and interp run one phase on its own, on the host or a GPU."""
 import ctypes as C
 
 import numpy as np
@@ -101,8 +104,93 @@ def set_spgemm_scratch(slots):
     check(lib.amg_set_spgemm_scratch(int(slots)))
 
 
+def _host_csr(h, values=True):
+    """(nrows, ncols, rowptr, col, val) numpy copies of an AmgHostCsr, then freed"""
+    from . import lib
+    try:
+        n, z = h.nrows, h.nnz
+        return (n, h.ncols, np.ctypeslib.as_array(h.rowptr, (n + 1,)).copy(),
+                np.ctypeslib.as_array(h.col, (z,)).copy() if z else np.zeros(0, np.int32),
+                (np.ctypeslib.as_array(h.val, (z,)).copy() if z else np.zeros(0)) if values else None)
+    finally:
+        lib.amg_host_csr_free(C.byref(h))
+
+
+def _csr_args(rowptr, col, val=None):
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    cj = np.ascontiguousarray(col, dtype=np.int32)
+    v = None if val is None else np.ascontiguousarray(val, dtype=np.float64)
+    if rp.size < 1 or cj.size < rp[-1] or (v is not None and v.size < rp[-1]):
+        raise ValueError("rowptr / col / val length")
+    return rp, cj, v
+
+
+def strength(n, rowptr, col, val, theta, max_row_sum=1.0, num_functions=1, device=-1):
+    """amg_csr_strength: the strength pattern S of a square CSR, (rowptr, col),
+    on the host (device -1) or on that GPU."""
+    from . import check, lib
+    rp, cj, v = _csr_args(rowptr, col, val)
+    if rp.size != int(n) + 1:
+        raise ValueError("strength: rowptr length")
+    h = abi.AmgHostCsr()
+    check(lib.amg_csr_strength(int(device), int(n), rp.ctypes.data_as(abi._ip), cj.ctypes.data_as(abi._ip),
+                               v.ctypes.data_as(abi._dp), float(theta), float(max_row_sum), int(num_functions),
+                               C.byref(h)))
+    return _host_csr(h, values=False)[2:4]
+
+
+def transpose(n, m, rowptr, col, val=None, device=-1):
+    """amg_csr_transpose: the transpose of an n x m CSR by the setup's rule,
+    (rowptr, col, val); val None: the pattern alone, (rowptr, col, None)."""
+    from . import check, lib
+    rp, cj, v = _csr_args(rowptr, col, val)
+    if rp.size != int(n) + 1:
+        raise ValueError("transpose: rowptr length")
+    h = abi.AmgHostCsr()
+    check(lib.amg_csr_transpose(int(device), int(n), int(m), rp.ctypes.data_as(abi._ip), cj.ctypes.data_as(abi._ip),
+                                None if v is None else v.ctypes.data_as(abi._dp), C.byref(h)))
+    return _host_csr(h, values=v is not None)[2:]
+
+
+def pmis(n, s_rowptr, s_col, seed, device=-1):
+    """amg_cf_pmis: the PMIS marker (1 = C, -1 = F) of a strength pattern; seed
+    is the per-level seed (include/amg_mi355x.h)."""
+    from . import check, lib
+    rp, cj, _ = _csr_args(s_rowptr, s_col)
+    if rp.size != int(n) + 1:
+        raise ValueError("pmis: rowptr length")
+    cf = np.zeros(int(n), dtype=np.int32)
+    check(lib.amg_cf_pmis(int(device), int(n), rp.ctypes.data_as(abi._ip), cj.ctypes.data_as(abi._ip),
+                          int(seed) & (2 ** 64 - 1), cf.ctypes.data_as(abi._ip)))
+    return cf
+
+
+def interp(n, rowptr, col, val, s_rowptr, s_col, cf, interp_type=AMG_CLASSICAL_EXT_I, num_functions=1, device=-1):
+    """amg_classical_interp: P of one level, (nrows, ncols, rowptr, col, val)."""
+    from . import check, lib
+    rp, cj, v = _csr_args(rowptr, col, val)
+    srp, scj, _ = _csr_args(s_rowptr, s_col)
+    c = np.ascontiguousarray(cf, dtype=np.int32)
+    if rp.size != int(n) + 1 or srp.size != int(n) + 1 or c.size != int(n):
+        raise ValueError("interp: rowptr / cf length")
+    h = abi.AmgHostCsr()
+    check(lib.amg_classical_interp(int(device), int(n), rp.ctypes.data_as(abi._ip), cj.ctypes.data_as(abi._ip),
+                                   v.ctypes.data_as(abi._dp), srp.ctypes.data_as(abi._ip),
+                                   scj.ctypes.data_as(abi._ip), c.ctypes.data_as(abi._ip), int(interp_type),
+                                   int(num_functions), C.byref(h)))
+    return _host_csr(h)
+
+
+def set_setup_scratch(slots):
+    """amg_set_setup_scratch: the device interpolation's scratch budget in
+    slots per batch of rows, process-wide; 0 restores the default."""
+    from . import check, lib
+    check(lib.amg_set_setup_scratch(int(slots)))
+
+
 class ClassicalAMG:
-    """Host hierarchy from a square CSR (diagonal first)."""
+    """Hierarchy (held on the host) from a square CSR (diagonal first); keywords
+    are the fields of amg_classical_opts, setup_on_device among them."""
 
     def __init__(self, n, rowptr, col, val, opts=None, **kw):
         from . import check, lib

@@ -23,6 +23,12 @@
 //                (add_P_max_elmts / add_trunc_factor)
 // Levels are built until the coarse operator has at most max_coarse_size rows,
 // coarsening stalls, or max_levels is reached.
+// The functions below are the host form and the definition.  opts.device moves
+// the products and the truncation to a GPU, opts.setup_on_device the whole
+// level loop (amg_setup_dev.hip: strength, S^T, PMIS, interpolation, R = P^T on
+// the device, bit-identical to strength / transpose_pattern / coarsen_pmis /
+// interpolation / transpose here); amg_csr_strength, amg_csr_transpose,
+// amg_cf_pmis and amg_classical_interp run one phase on its own.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -59,6 +65,20 @@ int amg_smooth_transfer_device(int device, int An, const std::vector<int> &arp, 
                                const std::vector<double> &rv, double w, int add_max, double add_tf,
                                std::vector<int> &psrp, std::vector<int> &pscj, std::vector<double> &psv,
                                std::vector<int> &rsrp, std::vector<int> &rscj, std::vector<double> &rsv);
+
+// amg_setup_dev.hip: strength, transposes, PMIS and interpolation on a GPU (host
+// CSR in and out), each bit-identical to its host function below, and the level
+// loop that keeps the hierarchy on the device (setup_on_device)
+int amg_strength_device(int device, int n, const int *rp, const int *cj, const double *v, double theta,
+                        double max_row_sum, int nfun, std::vector<int> &srp, std::vector<int> &scj);
+int amg_transpose_device(int device, int n, int m, const int *rp, const int *cj, const double *v_or_null,
+                         std::vector<int> &trp, std::vector<int> &tcj, std::vector<double> &tv);
+int amg_pmis_device(int device, int n, const int *srp, const int *scj, unsigned long long seed, int *cf, int *rounds);
+int amg_interp_device(int device, int n, const int *rp, const int *cj, const double *v, const int *srp, const int *scj,
+                      const int *cf, int type, int nfun, int *nc, std::vector<int> &prp, std::vector<int> &pcj,
+                      std::vector<double> &pv);
+int amg_classical_setup_device(const amg_classical_opts *o, int n, const int *rp, const int *cj, const double *v,
+                               const amg_hmis_fn &hmis, std::vector<amg_setup_dev_level> &levels);
 
 namespace {
 
@@ -579,6 +599,7 @@ extern "C" void amg_classical_opts_default(amg_classical_opts *o)
    o->device = -1;
    o->P_max_elmts = 0; // hypre's default (no -P_max_elmts): P as interpolation() leaves it
    o->trunc_factor = 0.0;
+   o->setup_on_device = 0;
 }
 
 extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int *rowptr, const int *col,
@@ -596,6 +617,8 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
    AMG_ARG(o->P_max_elmts >= 0 && o->trunc_factor >= 0.0 && o->trunc_factor <= 1.0,
            "amg_classical_setup: P_max_elmts %d, trunc_factor %g (>= 0, trunc_factor <= 1)", o->P_max_elmts,
            o->trunc_factor);
+   AMG_ARG(o->setup_on_device == 0 || (o->setup_on_device == 1 && o->device >= 0),
+           "amg_classical_setup: setup_on_device %d needs device >= 0 (device %d)", o->setup_on_device, o->device);
    const long long nnz = rowptr[n];
    AMG_ARG(rowptr[0] == 0 && nnz >= 0, "amg_classical_setup: rowptr");
    auto *H = new amg_classical();
@@ -610,6 +633,41 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
          return amg_set_error(AMG_ERR_ARG, "amg_classical_setup: column %d out of range", A0.cj[k]);
       }
    H->A.push_back(std::move(A0));
+   if (o->setup_on_device) {
+      for (int i = 0; i < n; i++)
+         if (rowptr[i + 1] < rowptr[i]) {
+            delete H;
+            return amg_set_error(AMG_ERR_ARG, "amg_classical_setup: rowptr decreases at row %d", i);
+         }
+      std::vector<amg_setup_dev_level> lv;
+      const amg_hmis_fn hmis = [](int sn, const std::vector<int> &srp, const std::vector<int> &scj,
+                                  std::vector<int> &cf) {
+         HCsr S, ST;
+         S.n = S.m = sn;
+         S.rp = srp;
+         S.cj = scj;
+         transpose_pattern(S, ST);
+         coarsen_rs(S, ST, cf);
+      };
+      const HCsr &A = H->A[0];
+      const int st = amg_classical_setup_device(o, n, A.rp.data(), A.cj.data(), A.v.data(), hmis, lv);
+      if (st != AMG_OK) {
+         delete H;
+         return st;
+      }
+      for (amg_setup_dev_level &L : lv) {
+         HCsr P, R, Ac;
+         P.n = L.n, P.m = L.nc, P.rp = std::move(L.prp), P.cj = std::move(L.pcj), P.v = std::move(L.pv);
+         R.n = L.nc, R.m = L.n, R.rp = std::move(L.rrp), R.cj = std::move(L.rcj), R.v = std::move(L.rv);
+         Ac.n = Ac.m = L.nc, Ac.rp = std::move(L.arp), Ac.cj = std::move(L.acj), Ac.v = std::move(L.av);
+         H->cf.push_back(std::move(L.cf));
+         H->P.push_back(std::move(P));
+         H->R.push_back(std::move(R));
+         H->A.push_back(std::move(Ac));
+      }
+      *out = H;
+      return AMG_OK;
+   }
    const uint64_t seed = o->coarsen_type == AMG_COARSEN_PMIS ? o->seed + 0x9e37ULL : o->seed;
    for (int l = 0; l + 1 < o->max_levels; l++) {
       const HCsr &A = H->A.back();
@@ -818,6 +876,130 @@ extern "C" int amg_csr_spgemm(int device, int An, int Am, const int *arp, const 
    out->ncols = Bm;
    out->nnz = (long long)nz;
    return AMG_OK;
+}
+
+// an amg_host_csr filled from M (values only when M has them)
+static int to_host_csr(const char *who, int n, int m, const std::vector<int> &rp, const std::vector<int> &cj,
+                       const std::vector<double> *v, amg_host_csr *out)
+{
+   const size_t nz = cj.size();
+   out->rowptr = (int *)std::malloc(sizeof(int) * ((size_t)n + 1));
+   out->col = (int *)std::malloc(sizeof(int) * std::max<size_t>(nz, 1));
+   out->val = v ? (double *)std::malloc(sizeof(double) * std::max<size_t>(nz, 1)) : nullptr;
+   if (!out->rowptr || !out->col || (v && !out->val)) {
+      amg_host_csr_free(out);
+      return amg_set_error(AMG_ERR_OOM, "%s: out of host memory", who);
+   }
+   std::copy(rp.begin(), rp.end(), out->rowptr);
+   std::copy(cj.begin(), cj.end(), out->col);
+   if (v) std::copy(v->begin(), v->end(), out->val);
+   out->nrows = n;
+   out->ncols = m;
+   out->nnz = (long long)nz;
+   return AMG_OK;
+}
+
+// rowptr / col of an n x m CSR as the setup phases need them
+static int check_pattern(const char *who, int n, int m, const int *rp, const int *cj)
+{
+   AMG_ARG(rp && rp[0] == 0, "%s: rowptr", who);
+   for (int i = 0; i < n; i++) AMG_ARG(rp[i + 1] >= rp[i], "%s: rowptr decreases at row %d", who, i);
+   AMG_ARG(rp[n] == 0 || cj, "%s: bad argument", who);
+   for (int k = 0; k < rp[n]; k++) AMG_ARG(cj[k] >= 0 && cj[k] < m, "%s: column %d outside [0, %d)", who, cj[k], m);
+   return AMG_OK;
+}
+
+static void wrap_csr(int n, int m, const int *rp, const int *cj, const double *v, HCsr &M)
+{
+   M.n = n, M.m = m;
+   M.rp.assign(rp, rp + n + 1);
+   M.cj.assign(cj, cj + rp[n]);
+   if (v) M.v.assign(v, v + rp[n]);
+}
+
+extern "C" int amg_csr_strength(int device, int n, const int *rowptr, const int *col, const double *val, double theta,
+                                double max_row_sum, int num_functions, amg_host_csr *S)
+{
+   AMG_ARG(S && n > 0 && num_functions >= 1, "amg_csr_strength: bad argument");
+   *S = amg_host_csr{};
+   AMG_TRY(check_pattern("amg_csr_strength", n, n, rowptr, col));
+   AMG_ARG(rowptr[n] == 0 || val, "amg_csr_strength: bad argument");
+   HCsr Sm;
+   if (device >= 0) {
+      AMG_TRY(amg_strength_device(device, n, rowptr, col, val, theta, max_row_sum, num_functions, Sm.rp, Sm.cj));
+   } else {
+      HCsr A;
+      wrap_csr(n, n, rowptr, col, val, A);
+      strength(A, theta, max_row_sum, num_functions, Sm);
+   }
+   return to_host_csr("amg_csr_strength", n, n, Sm.rp, Sm.cj, nullptr, S);
+}
+
+extern "C" int amg_csr_transpose(int device, int n, int m, const int *rowptr, const int *col, const double *val,
+                                 amg_host_csr *T)
+{
+   AMG_ARG(T && n > 0 && m > 0, "amg_csr_transpose: bad argument");
+   *T = amg_host_csr{};
+   AMG_TRY(check_pattern("amg_csr_transpose", n, m, rowptr, col));
+   HCsr Tm;
+   if (device >= 0) {
+      AMG_TRY(amg_transpose_device(device, n, m, rowptr, col, val, Tm.rp, Tm.cj, Tm.v));
+   } else {
+      HCsr A;
+      wrap_csr(n, m, rowptr, col, val, A);
+      if (val)
+         transpose(A, Tm);
+      else
+         transpose_pattern(A, Tm);
+   }
+   return to_host_csr("amg_csr_transpose", m, n, Tm.rp, Tm.cj, val ? &Tm.v : nullptr, T);
+}
+
+extern "C" int amg_cf_pmis(int device, int n, const int *s_rowptr, const int *s_col, unsigned long long seed, int *cf)
+{
+   AMG_ARG(cf && n > 0, "amg_cf_pmis: bad argument");
+   AMG_TRY(check_pattern("amg_cf_pmis", n, n, s_rowptr, s_col));
+   if (device >= 0) {
+      int rounds = 0;
+      AMG_TRY(amg_pmis_device(device, n, s_rowptr, s_col, seed, cf, &rounds));
+      if (std::getenv("AMG_CLASSICAL_TIMING")) std::fprintf(stderr, "[classical] PMIS n=%d: %d rounds\n", n, rounds);
+   } else {
+      HCsr S, ST;
+      wrap_csr(n, n, s_rowptr, s_col, nullptr, S);
+      transpose_pattern(S, ST);
+      std::vector<int> c;
+      coarsen_pmis(S, ST, seed, c);
+      std::copy(c.begin(), c.end(), cf);
+   }
+   return AMG_OK;
+}
+
+extern "C" int amg_classical_interp(int device, int n, const int *rowptr, const int *col, const double *val,
+                                    const int *s_rowptr, const int *s_col, const int *cf, int interp_type,
+                                    int num_functions, amg_host_csr *P)
+{
+   AMG_ARG(P && cf && n > 0 && num_functions >= 1, "amg_classical_interp: bad argument");
+   *P = amg_host_csr{};
+   AMG_ARG(interp_type == AMG_CLASSICAL_EXT_I || interp_type == AMG_CLASSICAL_DIRECT,
+           "amg_classical_interp: interp_type %d (3 direct, 6 extended+i)", interp_type);
+   AMG_TRY(check_pattern("amg_classical_interp: A", n, n, rowptr, col));
+   AMG_ARG(rowptr[n] == 0 || val, "amg_classical_interp: bad argument");
+   AMG_TRY(check_pattern("amg_classical_interp: S", n, n, s_rowptr, s_col));
+   for (int i = 0; i < n; i++)
+      AMG_ARG(cf[i] == CF_C || cf[i] == CF_F, "amg_classical_interp: cf[%d] = %d (1 = C, -1 = F)", i, cf[i]);
+   HCsr Pm;
+   int nc = 0;
+   if (device >= 0) {
+      AMG_TRY(amg_interp_device(device, n, rowptr, col, val, s_rowptr, s_col, cf, interp_type, num_functions, &nc,
+                                Pm.rp, Pm.cj, Pm.v));
+   } else {
+      HCsr A, S;
+      wrap_csr(n, n, rowptr, col, val, A);
+      wrap_csr(n, n, s_rowptr, s_col, nullptr, S);
+      const std::vector<int> c(cf, cf + n);
+      interpolation(A, S, c, interp_type, num_functions, Pm, &nc);
+   }
+   return to_host_csr("amg_classical_interp", n, nc, Pm.rp, Pm.cj, &Pm.v, P);
 }
 
 extern "C" int amg_classical_cf_marker(const amg_classical *H, int level, int *cf)

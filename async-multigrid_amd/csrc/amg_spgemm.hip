@@ -259,6 +259,14 @@ int download(hipStream_t s, const T *d, size_t n, std::vector<T> &h)
 
 } // namespace
 
+// spgemm_dev for the device-resident setup loop (amg_setup_dev.hip)
+int amg_spgemm_dev(hipStream_t s, int An, const int *d_arp, const int *d_acj, const double *d_av, const int *d_brp,
+                   const int *d_bcj, const double *d_bv, int Bm, int **d_crp, int **d_ccj, double **d_cv,
+                   long long *nnz)
+{
+   return spgemm_dev(s, An, d_arp, d_acj, d_av, d_brp, d_bcj, d_bv, Bm, d_crp, d_ccj, d_cv, nnz);
+}
+
 extern "C" int amg_set_spgemm_scratch(long long slots)
 {
    AMG_ARG(slots >= 0, "amg_set_spgemm_scratch: %lld slots", slots);

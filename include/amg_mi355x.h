@@ -547,7 +547,14 @@ int amg_gen_register(amg_ctx *ctx, const amg_gen *g, int which, int level, int z
  * SMEM_Setup.cpp:55-70 / DMEM_Setup.cpp:169-173, on the host).  hypre is not in
  * the reference tree: its published algorithms are restated, parity with
  * hypre's own hierarchies is unpinned.  Levels hold host CSR (A diagonal first,
- * P with sorted columns, R = P^T) until amg_classical_free. ------------------ */
+ * P with sorted columns, R = P^T) until amg_classical_free.  With device >= 0 the
+ * Galerkin products and the truncation run on that GPU between host phases; with
+ * setup_on_device as well the whole level loop does (strength, S^T, PMIS,
+ * interpolation, truncation, R = P^T, the products: amg_setup_dev.hip) and only
+ * each level's marker, P, R and coarse operator come back.  Every device phase
+ * is bit-identical to its host function, so the three paths build the same
+ * hierarchy; the phases are also callable on their own (amg_csr_strength, ...,
+ * at the end of this header). ------------------------------------------------ */
 #define AMG_COARSEN_PMIS 8        /* hypre coarsen_type 8                      */
 #define AMG_COARSEN_PMIS_FIXED 9  /* 9: PMIS with a fixed random sequence (DMEM) */
 #define AMG_COARSEN_HMIS 10       /* 10 (SMEM default)                         */
@@ -574,6 +581,12 @@ typedef struct {
                                either set each level's P is truncated (amg_csr_truncate's
                                rule) before R = P^T and the Galerkin product, on `device`
                                when that is >= 0 (amg_trunc.hip, bit-identical)      */
+   int setup_on_device;     /* 1 (needs device >= 0, else AMG_ERR_ARG): A_0 is uploaded
+                               once and every level's strength, S^T, PMIS, interpolation,
+                               truncation, R = P^T and products run on device arrays,
+                               A_{l+1} staying there as the next level's input; HMIS
+                               (coarsen_type 10) coarsens on the host from a downloaded
+                               S.  Same hierarchy, bit for bit.  0 (default): off     */
 } amg_classical_opts;
 void amg_classical_opts_default(amg_classical_opts *o); /* the SMEM parameters */
 int amg_classical_setup(const amg_classical_opts *o, int n, const int *rowptr, const int *col,
@@ -926,6 +939,53 @@ int amg_csr_spgemm(int device, int An, int Am, const int *arp, const int *acj, c
  * table alone is larger is a batch of its own.  0: the default, 1 << 29.  The
  * result does not depend on it.  slots < 0: AMG_ERR_ARG. */
 int amg_set_spgemm_scratch(long long slots);
+
+/* ---- the classical setup's other phases, on their own ---------------------------- */
+/* Each takes host CSR and runs the setup's own function: device -1 on the host,
+ * >= 0 on that GPU (amg_setup_dev.hip), bit-identical.  Operands are checked
+ * before anything is launched: n <= 0, rowptr[0] != 0, a decreasing rowptr or a
+ * column out of range is AMG_ERR_ARG.  Results come back in an amg_host_csr:
+ * release it with amg_host_csr_free. */
+/* strength of connection (hypre CreateS): with a_ii the row's last entry of
+ * column i (0 without one), the row scale is the smallest a_ij for a_ii >= 0
+ * (the largest for a_ii < 0) over j != i of the same function (j % num_functions
+ * == i % num_functions), never beyond 0; a_ij of such a j is strong when
+ * a_ij < theta x scale (> for a_ii < 0).  With max_row_sum < 1 a row whose
+ * |sum in storage order| exceeds max_row_sum |a_ii| has no strong entry.  S holds
+ * the strong columns of each row in storage order; S->val is NULL. */
+int amg_csr_strength(int device, int n, const int *rowptr, const int *col, const double *val,
+                     double theta, double max_row_sum, int num_functions, amg_host_csr *S);
+/* transpose of an n x m CSR: row c of T holds the source rows of column c
+ * ascending, a row's repeated column in storage order (the host's counting sort;
+ * on the device integer atomics count and entries are placed by rank).  val NULL:
+ * the pattern alone (T->val NULL). */
+int amg_csr_transpose(int device, int n, int m, const int *rowptr, const int *col, const double *val,
+                      amg_host_csr *T);
+/* PMIS on the strength pattern S (n x n): measure |S^T_i| + u_i with u_i =
+ * (splitmix64(seed ^ i x 0x2545f4914f6cdd1d) >> 11) 2^-53; points of measure < 1
+ * are F; then, in rounds, every undecided point whose measure exceeds that of
+ * every undecided neighbour in S and S^T (a tie blocks both) becomes C, and the
+ * undecided points that depend on a new C point become F; a round that selects
+ * nothing makes the rest F.  cf: n ints, 1 = C, -1 = F.  seed is the per-level
+ * seed: amg_classical_setup passes (seed, + 0x9e37 for coarsen_type 8) +
+ * 7919 x level. */
+int amg_cf_pmis(int device, int n, const int *s_rowptr, const int *s_col, unsigned long long seed,
+                int *cf);
+/* interpolation from A (n x n), S and the marker cf (every entry 1 or -1, else
+ * AMG_ERR_ARG): C rows inject; F rows by extended+i (interp_type 6) or direct
+ * (3), the formulas at the head of csrc/amg_classical.cpp with every sum in
+ * storage order, a_kk the first entry of column k, each a_ik abar_kj / d_k one
+ * multiply then one divide.  P is n x (number of C points), columns ascending;
+ * a row whose atil (direct: a_ii or the C sum) is 0 is empty. */
+int amg_classical_interp(int device, int n, const int *rowptr, const int *col, const double *val,
+                         const int *s_rowptr, const int *s_col, const int *cf, int interp_type,
+                         int num_functions, amg_host_csr *P);
+/* scratch budget of the device interpolation, process-wide: F rows run in
+ * batches whose scratch (per row |S_i| slots, for extended+i plus |S_k| for every
+ * strong F neighbour k; 16 bytes a slot) fits in `slots`; a row that needs more
+ * is a batch of its own.  0: the default, 1 << 27.  The result does not depend
+ * on it.  slots < 0: AMG_ERR_ARG. */
+int amg_set_setup_scratch(long long slots);
 
 #ifdef __cplusplus
 }

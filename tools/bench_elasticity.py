@@ -4,12 +4,17 @@ refined r times, Q1 byVDIM) on the in-house classical hierarchy
 parameters), SMEM_Solve MULT V(1,1) weighted Jacobi.  Prints one JSON line:
 V-cycle iterations/s, fine SpMV time and its bytes in the stored format, and
 per level the rows and entries per row.  --P-max-elmts / --trunc-factor build
-the hierarchy with truncated interpolation (the reference's -P_max_elmts)."""
+the hierarchy with truncated interpolation (the reference's -P_max_elmts).
+--gpu-setup 0 / 1 / 2: the classical setup on the host, with the Galerkin
+products on the GPU, or resident on the GPU (setup_on_device); setup_s carries
+the per-phase seconds of the library's AMG_CLASSICAL_TIMING lines."""
 import argparse
 import ctypes as C
 import json
 import os
+import re
 import sys
+import tempfile
 import time
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -27,7 +32,10 @@ def main():
     p.add_argument("--coarsen", type=int, default=9)
     p.add_argument("--theta", type=float, default=0.5)
     p.add_argument("--omega", type=float, default=0.6)
-    p.add_argument("--gpu-setup", type=int, default=1, help="Galerkin products on the GPU (classical opts.device)")
+    p.add_argument("--gpu-setup", type=int, default=1, choices=(0, 1, 2),
+                   help="1: Galerkin products on the GPU (classical opts.device); 2: the whole level loop "
+                        "(opts.setup_on_device); 0: host")
+    p.add_argument("--setup-only", action="store_true", help="print setup_s and stop before the solve")
     p.add_argument("--P-max-elmts", type=int, default=0, help="classical opts.P_max_elmts (0: no truncation)")
     p.add_argument("--trunc-factor", type=float, default=0.0, help="classical opts.trunc_factor (0: none)")
     p.add_argument("--async-ranks", type=int, default=0,
@@ -41,10 +49,21 @@ def main():
     t0 = time.time()
     n, rp, cj, v, b = amg.classical.elasticity(a.refine)
     t1 = time.time()
-    H = amg.classical.ClassicalAMG(n, rp, cj, v, coarsen_type=a.coarsen, strong_threshold=a.theta,
-                                   num_functions=3, device=0 if a.gpu_setup else -1,
-                                   P_max_elmts=a.P_max_elmts, trunc_factor=a.trunc_factor)
-    t2 = time.time()
+    with phase_log() as phases:
+        H = amg.classical.ClassicalAMG(n, rp, cj, v, coarsen_type=a.coarsen, strong_threshold=a.theta,
+                                       num_functions=3, device=0 if a.gpu_setup else -1,
+                                       setup_on_device=1 if a.gpu_setup == 2 else 0,
+                                       P_max_elmts=a.P_max_elmts, trunc_factor=a.trunc_factor)
+        t2 = time.time()
+    setup_s = {"generate": t1 - t0, "classical": t2 - t1,
+               "galerkin_on": "gpu" if a.gpu_setup else "host",
+               "setup_on": ("host", "host, products on gpu", "gpu")[a.gpu_setup],
+               "phases": {k: sum(lv[k] for lv in phases) for k in ("strength", "coarsen", "interp", "RAP")},
+               "per_level": phases}
+    if a.setup_only:
+        print(json.dumps({"workload": f"classical setup, DMEM elasticity r={a.refine}: {n} dofs", "levels": H.L,
+                          "setup_s": setup_s}), flush=True)
+        return
     print(f"[elast] r={a.refine}: {n} dofs, {len(cj)} nnz; generated {t1 - t0:.1f}s, classical setup "
           f"{t2 - t1:.1f}s, {H.L} levels", file=sys.stderr, flush=True)
     ctx = amg.Context(0, 4)
@@ -124,13 +143,45 @@ def main():
                         "alg_bytes_per_launch": spmv_bytes, "avg_launch_ms": ms.value},
            "coarse_spmv": coarse,
            "relres_after": rn / r0, "cycles": a.warmup + a.steps,
-           "setup_s": {"generate": t1 - t0, "classical": t2 - t1,
-                       "galerkin_on": "gpu" if a.gpu_setup else "host"}}
+           "setup_s": setup_s}
     Hd.free()
     ctx.close()
     if a.async_ranks:
         out["async_additive"] = async_leg(amg, H, b, a)
     print(json.dumps(out), flush=True)
+
+
+class phase_log:
+    """The library's per-level timing lines (AMG_CLASSICAL_TIMING, written to
+    stderr by the C code) captured while the block runs: a list of
+    {level, n, strength, coarsen, interp, RAP} in seconds; the lines are passed on."""
+    PAT = re.compile(r"\[classical\] level (\d+) n=(\d+): strength ([\d.]+)s coarsen ([\d.]+)s interp ([\d.]+)s "
+                     r"RAP ([\d.]+)s")
+
+    def __enter__(self):
+        self.rows = []
+        self.had = os.environ.get("AMG_CLASSICAL_TIMING")
+        os.environ["AMG_CLASSICAL_TIMING"] = "1"
+        sys.stderr.flush()
+        self.tmp = tempfile.TemporaryFile(mode="w+b")
+        self.saved = os.dup(2)
+        os.dup2(self.tmp.fileno(), 2)
+        return self.rows
+
+    def __exit__(self, *exc):
+        os.dup2(self.saved, 2)
+        os.close(self.saved)
+        if self.had is None:
+            del os.environ["AMG_CLASSICAL_TIMING"]
+        self.tmp.seek(0)
+        text = self.tmp.read().decode(errors="replace")
+        self.tmp.close()
+        sys.stderr.write(text)
+        sys.stderr.flush()
+        for m in self.PAT.finditer(text):
+            self.rows.append({"level": int(m[1]), "n": int(m[2]), "strength": float(m[3]), "coarsen": float(m[4]),
+                              "interp": float(m[5]), "RAP": float(m[6])})
+        return False
 
 
 def async_leg(amg, H, b, a):
