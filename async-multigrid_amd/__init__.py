@@ -255,6 +255,12 @@ class Mat:
         check(lib.amg_mat_download(self.ctx.h, self.h, _ip(rp), _ip(cj), _dp(cv)))
         return rp, cj[:self.nnz], cv[:self.nnz]
 
+    def bsr3_counts(self):
+        """Stored block count per block row of a blocked matrix (0: the block row keeps the CSR form)."""
+        out = np.empty(self.nrows // 3, dtype=np.uint8)
+        check(lib.amg_mat_bsr3_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
+
     def free(self):
         if self.h:
             lib.amg_mat_free(self.h)

@@ -1236,6 +1236,15 @@ extern "C" int amg_mat_bsr3_slice(const amg_mat *A)
    return A && A->bsr3 ? A->bsl : 0;
 }
 
+extern "C" int amg_mat_bsr3_counts(const amg_mat *A, unsigned char *out)
+{
+   AMG_ARG(A && out, "amg_mat_bsr3_counts: null argument");
+   AMG_ARG(A->bsr3 && A->bmode, "amg_mat_bsr3_counts: the matrix is not in 3x3 block form");
+   AMG_HIP(hipStreamSynchronize(A->ctx->stream));
+   AMG_HIP(hipMemcpy(out, A->bmode, (size_t)(A->nrows / 3), hipMemcpyDeviceToHost));
+   return AMG_OK;
+}
+
 extern "C" int amg_csr_register(amg_ctx *c, int nrows, int ncols, long long nnz, const int *rowptr,
                                 const int *col, const double *val, int diag_first, amg_mat **out)
 {

@@ -286,6 +286,10 @@ int amg_mat_bsr3(const amg_mat *A);
 /* block rows per slice of a blocked matrix: 64 (a lane per block row) or 21
  * (a lane per row); 0 when not blocked */
 int amg_mat_bsr3_slice(const amg_mat *A);
+/* the stored block count of every block row (out: nrows / 3 bytes, host): the
+ * array the block kernels walk, 1..255 blocks, 0 for a block row kept in CSR
+ * form; AMG_ERR_ARG when the matrix is not blocked */
+int amg_mat_bsr3_counts(const amg_mat *A, unsigned char *out);
 int amg_mat_plane_march(const amg_mat *A);
 int amg_mat_march_points(const amg_mat *A);
 int amg_mat_info(const amg_mat *A, int *nrows, int *ncols, long long *nnz);

@@ -16,11 +16,11 @@ def elast(amg):
     return {r: amg.classical.elasticity(r) for r in (2, 3)}
 
 
-def reg(ctx, n, rp, cj, v, bsr=1, vi=1):
+def reg(ctx, n, rp, cj, v, bsr=1, vi=1, diag_first=1):
     ctx.set_bsr3(bsr)
     ctx.set_value_index(vi)
     try:
-        return ctx.csr(n, n, rp, cj, v)
+        return ctx.csr(n, n, rp, cj, v, diag_first)
     finally:
         ctx.set_bsr3(2)
         ctx.set_value_index(1)
