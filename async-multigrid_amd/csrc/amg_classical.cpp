@@ -39,57 +39,9 @@
 #include <thread>
 #include <vector>
 
-#include "amg_internal.h"
-
-// amg_spgemm.hip: C = A B on a GPU, bit-identical to spgemm() below
-int amg_spgemm_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                      const std::vector<double> &av, int Bn, const std::vector<int> &brp,
-                      const std::vector<int> &bcj, const std::vector<double> &bv, int Bm, std::vector<int> &crp,
-                      std::vector<int> &ccj, std::vector<double> &cv);
-// A_c = R (A P) on a GPU with A P kept on the device, bit-identical to two spgemm() calls
-int amg_rap_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                   const std::vector<double> &av, const std::vector<int> &prp, const std::vector<int> &pcj,
-                   const std::vector<double> &pv, int Pm, int Rn, const std::vector<int> &rrp,
-                   const std::vector<int> &rcj, const std::vector<double> &rv, std::vector<int> &crp,
-                   std::vector<int> &ccj, std::vector<double> &cv);
-
-// amg_trunc.hip: rows truncated on a GPU, bit-identical to truncate_rows() below
-int amg_truncate_device(int device, int n, const int *rp, const int *cj, const double *v, double tf, int maxel,
-                        std::vector<int> &orp, std::vector<int> &ocj, std::vector<double> &ov);
-// amg_spgemm.hip: one level's SmoothTransfer on a GPU (P~ truncated there when an
-// add_* option is set, R~ then left to the caller), bit-identical to the host's
-int amg_smooth_transfer_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                               const std::vector<double> &av, const std::vector<int> &prp,
-                               const std::vector<int> &pcj, const std::vector<double> &pv, int Pm,
-                               const std::vector<int> &rrp, const std::vector<int> &rcj,
-                               const std::vector<double> &rv, double w, int add_max, double add_tf,
-                               std::vector<int> &psrp, std::vector<int> &pscj, std::vector<double> &psv,
-                               std::vector<int> &rsrp, std::vector<int> &rscj, std::vector<double> &rsv);
-
-// amg_setup_dev.hip: strength, transposes, PMIS and interpolation on a GPU (host
-// CSR in and out), each bit-identical to its host function below, and the level
-// loop that keeps the hierarchy on the device (setup_on_device)
-int amg_strength_device(int device, int n, const int *rp, const int *cj, const double *v, double theta,
-                        double max_row_sum, int nfun, std::vector<int> &srp, std::vector<int> &scj);
-int amg_transpose_device(int device, int n, int m, const int *rp, const int *cj, const double *v_or_null,
-                         std::vector<int> &trp, std::vector<int> &tcj, std::vector<double> &tv);
-int amg_pmis_device(int device, int n, const int *srp, const int *scj, unsigned long long seed, int *cf, int *rounds);
-int amg_interp_device(int device, int n, const int *rp, const int *cj, const double *v, const int *srp, const int *scj,
-                      const int *cf, int type, int nfun, int *nc, std::vector<int> &prp, std::vector<int> &pcj,
-                      std::vector<double> &pv);
-int amg_classical_setup_device(const amg_classical_opts *o, int n, const int *rp, const int *cj, const double *v,
-                               const amg_hmis_fn &hmis, std::vector<amg_setup_dev_level> &levels);
+#include "amg_csr.h" // HCsr, and the GPU paths' entry points (amg_spgemm.hip, amg_trunc.hip, amg_setup_dev.hip)
 
 namespace {
-
-struct HCsr {
-   int n = 0, m = 0;
-   std::vector<int> rp{0}, cj;
-   std::vector<double> v;
-   long long nnz() const { return (long long)cj.size(); }
-};
-
-constexpr int CF_U = 0, CF_C = 1, CF_F = -1;
 
 // host threads for the row-parallel setup phases (strength, interpolation):
 // AMG_SETUP_THREADS (any level of at least 64 rows), else the hardware's, at
@@ -266,9 +218,12 @@ void spgemm(const HCsr &A, const HCsr &B, HCsr &C)
 // Sums run in storage order.  A pass that drops nothing leaves the row as it is
 // (s and k are then the same sum).  The tie rule is this library's: hypre's
 // follows its quicksort.
-void truncate_rows(int n, const int *rp, const int *mcj, const double *mv, double tf, int maxel, HCsr &T)
+void truncate_rows(const HCsrView &M, double tf, int maxel, HCsr &T)
 {
-   rows_parallel(n, T, [&](int r0, int r1, std::vector<int> &cnt, std::vector<int> &cj, std::vector<double> &v) {
+   const int *rp = M.rp, *mcj = M.cj;
+   const double *mv = M.v;
+   T.n = M.n, T.m = M.m;
+   rows_parallel(M.n, T, [&](int r0, int r1, std::vector<int> &cnt, std::vector<int> &cj, std::vector<double> &v) {
       std::vector<int> c, ord;
       std::vector<double> w;
       std::vector<char> keep;
@@ -326,26 +281,12 @@ void truncate_rows(int n, const int *rp, const int *mcj, const double *mv, doubl
    });
 }
 
-// M's rows truncated in place, on the host or on GPU `device`
-int truncate_csr(HCsr &M, double tf, int maxel, int device)
+// T = M's rows truncated, on the host or on GPU `device`
+int truncate_csr(const HCsrView &M, double tf, int maxel, int device, HCsr &T)
 {
-   HCsr T;
-   T.n = M.n;
-   T.m = M.m;
-   if (device >= 0)
-      AMG_TRY(amg_truncate_device(device, M.n, M.rp.data(), M.cj.data(), M.v.data(), tf, maxel, T.rp, T.cj, T.v));
-   else
-      truncate_rows(M.n, M.rp.data(), M.cj.data(), M.v.data(), tf, maxel, T);
-   M = std::move(T);
+   if (device >= 0) return amg_truncate_device(device, M, tf, maxel, T);
+   truncate_rows(M, tf, maxel, T);
    return AMG_OK;
-}
-
-uint64_t splitmix64(uint64_t x)
-{
-   x += 0x9e3779b97f4a7c15ULL;
-   x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-   x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-   return x ^ (x >> 31);
 }
 
 // Ruge-Stueben first pass (the whole of HMIS in one process): pick the
@@ -640,30 +581,21 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
             return amg_set_error(AMG_ERR_ARG, "amg_classical_setup: rowptr decreases at row %d", i);
          }
       std::vector<amg_setup_dev_level> lv;
-      const amg_hmis_fn hmis = [](int sn, const std::vector<int> &srp, const std::vector<int> &scj,
-                                  std::vector<int> &cf) {
-         HCsr S, ST;
-         S.n = S.m = sn;
-         S.rp = srp;
-         S.cj = scj;
+      const amg_hmis_fn hmis = [](const HCsr &S, std::vector<int> &cf) {
+         HCsr ST;
          transpose_pattern(S, ST);
          coarsen_rs(S, ST, cf);
       };
-      const HCsr &A = H->A[0];
-      const int st = amg_classical_setup_device(o, n, A.rp.data(), A.cj.data(), A.v.data(), hmis, lv);
+      const int st = amg_classical_setup_device(o, H->A[0], hmis, lv);
       if (st != AMG_OK) {
          delete H;
          return st;
       }
       for (amg_setup_dev_level &L : lv) {
-         HCsr P, R, Ac;
-         P.n = L.n, P.m = L.nc, P.rp = std::move(L.prp), P.cj = std::move(L.pcj), P.v = std::move(L.pv);
-         R.n = L.nc, R.m = L.n, R.rp = std::move(L.rrp), R.cj = std::move(L.rcj), R.v = std::move(L.rv);
-         Ac.n = Ac.m = L.nc, Ac.rp = std::move(L.arp), Ac.cj = std::move(L.acj), Ac.v = std::move(L.av);
          H->cf.push_back(std::move(L.cf));
-         H->P.push_back(std::move(P));
-         H->R.push_back(std::move(R));
-         H->A.push_back(std::move(Ac));
+         H->P.push_back(std::move(L.P));
+         H->R.push_back(std::move(L.R));
+         H->A.push_back(std::move(L.Ac));
       }
       *out = H;
       return AMG_OK;
@@ -692,18 +624,18 @@ extern "C" int amg_classical_setup(const amg_classical_opts *o, int n, const int
       auto t3 = now();
       if (nc == 0 || nc == A.n) break; // coarsening stalled
       if (o->P_max_elmts > 0 || o->trunc_factor > 0.0) {
-         const int st = truncate_csr(P, o->trunc_factor, o->P_max_elmts, o->device);
+         HCsr T;
+         const int st = truncate_csr(view(P), o->trunc_factor, o->P_max_elmts, o->device, T);
          if (st != AMG_OK) {
             delete H;
             return st;
          }
+         P = std::move(T);
       }
       HCsr R, AP, Ac;
       transpose(P, R);
       if (o->device >= 0) {
-         Ac.n = R.n, Ac.m = P.m;
-         const int st = amg_rap_device(o->device, A.n, A.rp, A.cj, A.v, P.rp, P.cj, P.v, P.m, R.n, R.rp, R.cj, R.v,
-                                       Ac.rp, Ac.cj, Ac.v);
+         const int st = amg_rap_device(o->device, A, P, R, Ac);
          if (st != AMG_OK) {
             delete H;
             return st;
@@ -779,11 +711,8 @@ extern "C" int amg_classical_smooth_transfers(amg_classical *H, double w, int ad
          AMG_ARG(A.rp[i + 1] > A.rp[i] && A.cj[A.rp[i]] == i,
                  "amg_classical_smooth_transfers: level %d row %d has no leading diagonal", (int)l, i);
       HCsr &Ps = PS[l], &Rs = RS[l];
-      Ps.n = P.n, Ps.m = P.m, Rs.n = R.n, Rs.m = R.m;
       if (device >= 0) {
-         AMG_TRY(amg_smooth_transfer_device(device, A.n, A.rp, A.cj, A.v, P.rp, P.cj, P.v, P.m, R.rp, R.cj, R.v, w,
-                                            add_P_max_elmts, add_trunc_factor, Ps.rp, Ps.cj, Ps.v, Rs.rp, Rs.cj,
-                                            Rs.v));
+         AMG_TRY(amg_smooth_transfer_device(device, A, P, R, w, add_P_max_elmts, add_trunc_factor, Ps, Rs));
       } else {
          // or_smooth_transfer's arithmetic: G = I - w D^-1 A on A's pattern
          HCsr G = A;
@@ -793,7 +722,9 @@ extern "C" int amg_classical_smooth_transfers(amg_classical *H, double w, int ad
          }
          spgemm(G, P, Ps);
          if (trunc) {
-            AMG_TRY(truncate_csr(Ps, add_trunc_factor, add_P_max_elmts, -1));
+            HCsr T;
+            truncate_rows(view(Ps), add_trunc_factor, add_P_max_elmts, T);
+            Ps = std::move(T);
          } else {
             for (int i = 0; i < A.n; i++)
                for (int k = A.rp[i] + 1; k < A.rp[i + 1]; k++) G.v[k] = -w * A.v[k] / A.v[A.rp[A.cj[k]]];
@@ -807,6 +738,14 @@ extern "C" int amg_classical_smooth_transfers(amg_classical *H, double w, int ad
    return AMG_OK;
 }
 
+// M's arrays copied to the caller's (val only when asked for)
+static void copy_out(const HCsr &M, bool values, int *rowptr, int *col, double *val)
+{
+   std::copy(M.rp.begin(), M.rp.end(), rowptr);
+   std::copy(M.cj.begin(), M.cj.end(), col);
+   if (values) std::copy(M.v.begin(), M.v.end(), val);
+}
+
 extern "C" int amg_csr_truncate(int device, int n, const int *rowptr, const int *col, const double *val,
                                 double trunc_factor, int max_elmts, int *out_rowptr, int *out_col, double *out_val,
                                 long long *out_nnz)
@@ -817,26 +756,50 @@ extern "C" int amg_csr_truncate(int device, int n, const int *rowptr, const int 
    for (int i = 0; i < n; i++) AMG_ARG(rowptr[i + 1] >= rowptr[i], "amg_csr_truncate: rowptr decreases at row %d", i);
    AMG_ARG(rowptr[n] == 0 || (col && val && out_col && out_val), "amg_csr_truncate: bad argument");
    HCsr T;
-   if (device >= 0)
-      AMG_TRY(amg_truncate_device(device, n, rowptr, col, val, trunc_factor, max_elmts, T.rp, T.cj, T.v));
-   else
-      truncate_rows(n, rowptr, col, val, trunc_factor, max_elmts, T);
-   std::copy(T.rp.begin(), T.rp.end(), out_rowptr);
-   std::copy(T.cj.begin(), T.cj.end(), out_col);
-   std::copy(T.v.begin(), T.v.end(), out_val);
+   AMG_TRY(truncate_csr({n, 0, rowptr, col, val}, trunc_factor, max_elmts, device, T)); // columns: not needed
+   copy_out(T, true, out_rowptr, out_col, out_val);
    *out_nnz = T.nnz();
    return AMG_OK;
 }
 
-// rowptr / col of an n x m CSR as the callers of spgemm() need them
-static int check_csr(const char *who, int n, int m, const int *rp, const int *cj, const double *v)
+// an amg_host_csr filled from M
+static int to_host_csr(const char *who, const HCsr &M, bool values, amg_host_csr *out)
 {
-   AMG_ARG(rp && rp[0] == 0, "amg_csr_spgemm: %s: rowptr", who);
-   for (int i = 0; i < n; i++) AMG_ARG(rp[i + 1] >= rp[i], "amg_csr_spgemm: %s: rowptr decreases at row %d", who, i);
-   AMG_ARG(rp[n] == 0 || (cj && v), "amg_csr_spgemm: %s: bad argument", who);
-   for (int k = 0; k < rp[n]; k++)
-      AMG_ARG(cj[k] >= 0 && cj[k] < m, "amg_csr_spgemm: %s: column %d outside [0, %d)", who, cj[k], m);
+   const size_t nz = M.cj.size();
+   out->rowptr = (int *)std::malloc(sizeof(int) * ((size_t)M.n + 1));
+   out->col = (int *)std::malloc(sizeof(int) * std::max<size_t>(nz, 1));
+   out->val = values ? (double *)std::malloc(sizeof(double) * std::max<size_t>(nz, 1)) : nullptr;
+   if (!out->rowptr || !out->col || (values && !out->val)) {
+      amg_host_csr_free(out);
+      return amg_set_error(AMG_ERR_OOM, "%s: out of host memory", who);
+   }
+   copy_out(M, values, out->rowptr, out->col, out->val);
+   out->nrows = M.n;
+   out->ncols = M.m;
+   out->nnz = (long long)nz;
    return AMG_OK;
+}
+
+// rowptr / col of a CSR as the setup phases need them, and val where there are
+// entries when the caller needs values
+static int check_pattern(const char *who, const HCsrView &M, bool values)
+{
+   AMG_ARG(M.rp && M.rp[0] == 0, "%s: rowptr", who);
+   for (int i = 0; i < M.n; i++) AMG_ARG(M.rp[i + 1] >= M.rp[i], "%s: rowptr decreases at row %d", who, i);
+   AMG_ARG(M.rp[M.n] == 0 || (M.cj && (M.v || !values)), "%s: bad argument", who);
+   for (int k = 0; k < M.rp[M.n]; k++)
+      AMG_ARG(M.cj[k] >= 0 && M.cj[k] < M.m, "%s: column %d outside [0, %d)", who, M.cj[k], M.m);
+   return AMG_OK;
+}
+
+static HCsr copy_csr(const HCsrView &V)
+{
+   HCsr M;
+   M.n = V.n, M.m = V.m;
+   M.rp.assign(V.rp, V.rp + V.n + 1);
+   M.cj.assign(V.cj, V.cj + V.nnz());
+   if (V.v) M.v.assign(V.v, V.v + V.nnz());
+   return M;
 }
 
 extern "C" int amg_csr_spgemm(int device, int An, int Am, const int *arp, const int *acj, const double *av, int Bm,
@@ -844,77 +807,15 @@ extern "C" int amg_csr_spgemm(int device, int An, int Am, const int *arp, const 
 {
    AMG_ARG(out && An > 0 && Am > 0 && Bm > 0, "amg_csr_spgemm: bad argument");
    *out = amg_host_csr{};
-   AMG_TRY(check_csr("A", An, Am, arp, acj, av));
-   AMG_TRY(check_csr("B", Am, Bm, brp, bcj, bv));
-   HCsr A, B, Cm;
-   A.n = An, A.m = Am;
-   A.rp.assign(arp, arp + An + 1);
-   A.cj.assign(acj, acj + arp[An]);
-   A.v.assign(av, av + arp[An]);
-   B.n = Am, B.m = Bm;
-   B.rp.assign(brp, brp + Am + 1);
-   B.cj.assign(bcj, bcj + brp[Am]);
-   B.v.assign(bv, bv + brp[Am]);
-   if (device >= 0) {
-      Cm.n = An, Cm.m = Bm;
-      AMG_TRY(amg_spgemm_device(device, An, A.rp, A.cj, A.v, Am, B.rp, B.cj, B.v, Bm, Cm.rp, Cm.cj, Cm.v));
-   } else {
+   AMG_TRY(check_pattern("amg_csr_spgemm: A", {An, Am, arp, acj, av}, true));
+   AMG_TRY(check_pattern("amg_csr_spgemm: B", {Am, Bm, brp, bcj, bv}, true));
+   const HCsr A = copy_csr({An, Am, arp, acj, av}), B = copy_csr({Am, Bm, brp, bcj, bv});
+   HCsr Cm;
+   if (device >= 0)
+      AMG_TRY(amg_spgemm_device(device, A, B, Cm));
+   else
       spgemm(A, B, Cm);
-   }
-   const size_t nz = Cm.cj.size();
-   out->rowptr = (int *)std::malloc(sizeof(int) * ((size_t)An + 1));
-   out->col = (int *)std::malloc(sizeof(int) * std::max<size_t>(nz, 1));
-   out->val = (double *)std::malloc(sizeof(double) * std::max<size_t>(nz, 1));
-   if (!out->rowptr || !out->col || !out->val) {
-      amg_host_csr_free(out);
-      return amg_set_error(AMG_ERR_OOM, "amg_csr_spgemm: out of host memory");
-   }
-   std::copy(Cm.rp.begin(), Cm.rp.end(), out->rowptr);
-   std::copy(Cm.cj.begin(), Cm.cj.end(), out->col);
-   std::copy(Cm.v.begin(), Cm.v.end(), out->val);
-   out->nrows = An;
-   out->ncols = Bm;
-   out->nnz = (long long)nz;
-   return AMG_OK;
-}
-
-// an amg_host_csr filled from M (values only when M has them)
-static int to_host_csr(const char *who, int n, int m, const std::vector<int> &rp, const std::vector<int> &cj,
-                       const std::vector<double> *v, amg_host_csr *out)
-{
-   const size_t nz = cj.size();
-   out->rowptr = (int *)std::malloc(sizeof(int) * ((size_t)n + 1));
-   out->col = (int *)std::malloc(sizeof(int) * std::max<size_t>(nz, 1));
-   out->val = v ? (double *)std::malloc(sizeof(double) * std::max<size_t>(nz, 1)) : nullptr;
-   if (!out->rowptr || !out->col || (v && !out->val)) {
-      amg_host_csr_free(out);
-      return amg_set_error(AMG_ERR_OOM, "%s: out of host memory", who);
-   }
-   std::copy(rp.begin(), rp.end(), out->rowptr);
-   std::copy(cj.begin(), cj.end(), out->col);
-   if (v) std::copy(v->begin(), v->end(), out->val);
-   out->nrows = n;
-   out->ncols = m;
-   out->nnz = (long long)nz;
-   return AMG_OK;
-}
-
-// rowptr / col of an n x m CSR as the setup phases need them
-static int check_pattern(const char *who, int n, int m, const int *rp, const int *cj)
-{
-   AMG_ARG(rp && rp[0] == 0, "%s: rowptr", who);
-   for (int i = 0; i < n; i++) AMG_ARG(rp[i + 1] >= rp[i], "%s: rowptr decreases at row %d", who, i);
-   AMG_ARG(rp[n] == 0 || cj, "%s: bad argument", who);
-   for (int k = 0; k < rp[n]; k++) AMG_ARG(cj[k] >= 0 && cj[k] < m, "%s: column %d outside [0, %d)", who, cj[k], m);
-   return AMG_OK;
-}
-
-static void wrap_csr(int n, int m, const int *rp, const int *cj, const double *v, HCsr &M)
-{
-   M.n = n, M.m = m;
-   M.rp.assign(rp, rp + n + 1);
-   M.cj.assign(cj, cj + rp[n]);
-   if (v) M.v.assign(v, v + rp[n]);
+   return to_host_csr("amg_csr_spgemm", Cm, true, out);
 }
 
 extern "C" int amg_csr_strength(int device, int n, const int *rowptr, const int *col, const double *val, double theta,
@@ -922,17 +823,15 @@ extern "C" int amg_csr_strength(int device, int n, const int *rowptr, const int 
 {
    AMG_ARG(S && n > 0 && num_functions >= 1, "amg_csr_strength: bad argument");
    *S = amg_host_csr{};
-   AMG_TRY(check_pattern("amg_csr_strength", n, n, rowptr, col));
+   const HCsrView A{n, n, rowptr, col, val};
+   AMG_TRY(check_pattern("amg_csr_strength", A, false));
    AMG_ARG(rowptr[n] == 0 || val, "amg_csr_strength: bad argument");
    HCsr Sm;
-   if (device >= 0) {
-      AMG_TRY(amg_strength_device(device, n, rowptr, col, val, theta, max_row_sum, num_functions, Sm.rp, Sm.cj));
-   } else {
-      HCsr A;
-      wrap_csr(n, n, rowptr, col, val, A);
-      strength(A, theta, max_row_sum, num_functions, Sm);
-   }
-   return to_host_csr("amg_csr_strength", n, n, Sm.rp, Sm.cj, nullptr, S);
+   if (device >= 0)
+      AMG_TRY(amg_strength_device(device, A, theta, max_row_sum, num_functions, Sm));
+   else
+      strength(copy_csr(A), theta, max_row_sum, num_functions, Sm);
+   return to_host_csr("amg_csr_strength", Sm, false, S);
 }
 
 extern "C" int amg_csr_transpose(int device, int n, int m, const int *rowptr, const int *col, const double *val,
@@ -940,32 +839,30 @@ extern "C" int amg_csr_transpose(int device, int n, int m, const int *rowptr, co
 {
    AMG_ARG(T && n > 0 && m > 0, "amg_csr_transpose: bad argument");
    *T = amg_host_csr{};
-   AMG_TRY(check_pattern("amg_csr_transpose", n, m, rowptr, col));
+   const HCsrView A{n, m, rowptr, col, val};
+   AMG_TRY(check_pattern("amg_csr_transpose", A, false));
    HCsr Tm;
-   if (device >= 0) {
-      AMG_TRY(amg_transpose_device(device, n, m, rowptr, col, val, Tm.rp, Tm.cj, Tm.v));
-   } else {
-      HCsr A;
-      wrap_csr(n, m, rowptr, col, val, A);
-      if (val)
-         transpose(A, Tm);
-      else
-         transpose_pattern(A, Tm);
-   }
-   return to_host_csr("amg_csr_transpose", m, n, Tm.rp, Tm.cj, val ? &Tm.v : nullptr, T);
+   if (device >= 0)
+      AMG_TRY(amg_transpose_device(device, A, Tm));
+   else if (val)
+      transpose(copy_csr(A), Tm);
+   else
+      transpose_pattern(copy_csr(A), Tm);
+   return to_host_csr("amg_csr_transpose", Tm, val != nullptr, T);
 }
 
 extern "C" int amg_cf_pmis(int device, int n, const int *s_rowptr, const int *s_col, unsigned long long seed, int *cf)
 {
    AMG_ARG(cf && n > 0, "amg_cf_pmis: bad argument");
-   AMG_TRY(check_pattern("amg_cf_pmis", n, n, s_rowptr, s_col));
+   const HCsrView Sv{n, n, s_rowptr, s_col, nullptr};
+   AMG_TRY(check_pattern("amg_cf_pmis", Sv, false));
    if (device >= 0) {
       int rounds = 0;
-      AMG_TRY(amg_pmis_device(device, n, s_rowptr, s_col, seed, cf, &rounds));
+      AMG_TRY(amg_pmis_device(device, Sv, seed, cf, &rounds));
       if (std::getenv("AMG_CLASSICAL_TIMING")) std::fprintf(stderr, "[classical] PMIS n=%d: %d rounds\n", n, rounds);
    } else {
-      HCsr S, ST;
-      wrap_csr(n, n, s_rowptr, s_col, nullptr, S);
+      const HCsr S = copy_csr(Sv);
+      HCsr ST;
       transpose_pattern(S, ST);
       std::vector<int> c;
       coarsen_pmis(S, ST, seed, c);
@@ -982,24 +879,20 @@ extern "C" int amg_classical_interp(int device, int n, const int *rowptr, const 
    *P = amg_host_csr{};
    AMG_ARG(interp_type == AMG_CLASSICAL_EXT_I || interp_type == AMG_CLASSICAL_DIRECT,
            "amg_classical_interp: interp_type %d (3 direct, 6 extended+i)", interp_type);
-   AMG_TRY(check_pattern("amg_classical_interp: A", n, n, rowptr, col));
+   const HCsrView A{n, n, rowptr, col, val}, S{n, n, s_rowptr, s_col, nullptr};
+   AMG_TRY(check_pattern("amg_classical_interp: A", A, false));
    AMG_ARG(rowptr[n] == 0 || val, "amg_classical_interp: bad argument");
-   AMG_TRY(check_pattern("amg_classical_interp: S", n, n, s_rowptr, s_col));
+   AMG_TRY(check_pattern("amg_classical_interp: S", S, false));
    for (int i = 0; i < n; i++)
       AMG_ARG(cf[i] == CF_C || cf[i] == CF_F, "amg_classical_interp: cf[%d] = %d (1 = C, -1 = F)", i, cf[i]);
    HCsr Pm;
-   int nc = 0;
    if (device >= 0) {
-      AMG_TRY(amg_interp_device(device, n, rowptr, col, val, s_rowptr, s_col, cf, interp_type, num_functions, &nc,
-                                Pm.rp, Pm.cj, Pm.v));
+      AMG_TRY(amg_interp_device(device, A, S, cf, interp_type, num_functions, Pm));
    } else {
-      HCsr A, S;
-      wrap_csr(n, n, rowptr, col, val, A);
-      wrap_csr(n, n, s_rowptr, s_col, nullptr, S);
-      const std::vector<int> c(cf, cf + n);
-      interpolation(A, S, c, interp_type, num_functions, Pm, &nc);
+      int nc = 0;
+      interpolation(copy_csr(A), copy_csr(S), std::vector<int>(cf, cf + n), interp_type, num_functions, Pm, &nc);
    }
-   return to_host_csr("amg_classical_interp", n, nc, Pm.rp, Pm.cj, &Pm.v, P);
+   return to_host_csr("amg_classical_interp", Pm, true, P);
 }
 
 extern "C" int amg_classical_cf_marker(const amg_classical *H, int level, int *cf)

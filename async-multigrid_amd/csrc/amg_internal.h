@@ -38,16 +38,6 @@ int amg_set_error(int code, const char *fmt, ...);
       if (!(cond)) return amg_set_error(AMG_ERR_ARG, __VA_ARGS__);                         \
    } while (0)
 
-// amg_setup_dev.hip: what the device-resident classical level loop hands back
-// per level -- the C/F marker, P (n x nc), R = P^T and the coarse operator --
-// and the host coarsening it calls for HMIS (S's rowptr / col in, marker out)
-struct amg_setup_dev_level {
-   int n = 0, nc = 0;
-   std::vector<int> cf, prp, pcj, rrp, rcj, arp, acj;
-   std::vector<double> pv, rv, av;
-};
-using amg_hmis_fn = std::function<void(int n, const std::vector<int> &srp, const std::vector<int> &scj, std::vector<int> &cf)>;
-
 // rows handled by one workgroup of the CSR tile kernels (one row per lane)
 constexpr int AMG_TILE_ROWS = 256;
 // products staged per LDS chunk in the CSR tile kernels (16 KiB of fp64)

@@ -36,89 +36,29 @@
 // every entry with the whole row, 64 entries at a time: exact and without
 // atomics, quadratic in a row's length, which is tens of entries on the setup's
 // operators and a few hundred at a hub.
-// Offsets are 32-bit, as everywhere in the classical setup.
+// Offsets are 32-bit, as everywhere in the classical setup.  The phases take and
+// return device CSRs (amg_csr.h's DCsr, with the buffers, uploads, count scan and
+// row batching they share with amg_spgemm.hip and amg_trunc.hip).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <numeric>
 #include <vector>
 
-#include "amg_internal.h"
-
-// amg_spgemm.hip / amg_trunc.hip: device CSR in, device CSR out
-int amg_spgemm_dev(hipStream_t s, int An, const int *d_arp, const int *d_acj, const double *d_av, const int *d_brp,
-                   const int *d_bcj, const double *d_bv, int Bm, int **d_crp, int **d_ccj, double **d_cv,
-                   long long *nnz);
-int amg_trunc_dev(hipStream_t s, int n, const int *d_rp, const int *d_cj, const double *d_v, long long nnz, double tf,
-                  int maxel, int **d_orp, int **d_ocj, double **d_ov, long long *onnz);
+#include "amg_csr.h"
 
 namespace {
 
-constexpr int CF_U = 0, CF_C = 1, CF_F = -1;
 constexpr int WBLOCK = 256; // 4 wavefronts: 4 rows in flight per workgroup
 
 // scratch budget of one batch of interp_dev, in slots of 16 bytes (amg_set_setup_scratch)
 constexpr long long SETUP_BUDGET = 1LL << 27;
 std::atomic<long long> g_setup_budget{SETUP_BUDGET};
 
-struct DCsr {
-   int n = 0, m = 0;
-   long long nnz = 0;
-   int *rp = nullptr, *cj = nullptr;
-   double *v = nullptr;
-   void release()
-   {
-      hipFree(rp), hipFree(cj), hipFree(v);
-      rp = cj = nullptr, v = nullptr;
-      nnz = 0;
-   }
-};
-
 int wave_grid(int n) { return (int)std::max<long long>(1, std::min<long long>(((long long)n + 3) / 4, 8192)); }
-
-template <class T>
-int dalloc(T **d, size_t count)
-{
-   AMG_HIP(hipMalloc(d, std::max<size_t>(count, 1) * sizeof(T)));
-   return AMG_OK;
-}
-
-template <class T>
-int dput(hipStream_t s, const T *h, size_t count, T **d)
-{
-   AMG_TRY(dalloc(d, count));
-   if (count) AMG_HIP(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-   return AMG_OK;
-}
-
-template <class T>
-int dget(hipStream_t s, const T *d, size_t count, std::vector<T> &h)
-{
-   h.resize(count);
-   if (count) AMG_HIP(hipMemcpyAsync(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, s));
-   return AMG_OK;
-}
-
-// rowptr of n rows from their counts (scanned on the host, spgemm_dev's scheme:
-// the total sizes the output); *d_rp allocated here
-int scan_counts(hipStream_t s, const int *d_cnt, int n, int **d_rp, long long *total)
-{
-   std::vector<int> cnt, rp((size_t)n + 1, 0);
-   AMG_TRY(dget(s, d_cnt, (size_t)n, cnt));
-   AMG_HIP(hipStreamSynchronize(s));
-   long long t = 0;
-   for (int i = 0; i < n; i++) {
-      t += cnt[i];
-      if (t > INT_MAX) return amg_set_error(AMG_ERR_ARG, "classical setup on the device: more than 2^31 - 1 entries");
-      rp[i + 1] = (int)t;
-   }
-   AMG_TRY(dput(s, rp.data(), (size_t)n + 1, d_rp));
-   AMG_HIP(hipStreamSynchronize(s)); // rp leaves scope
-   *total = t;
-   return AMG_OK;
-}
 
 // ---- strength -------------------------------------------------------------------
 __global__ __launch_bounds__(WBLOCK) void strength_flag_k(const int *__restrict__ rp, const int *__restrict__ cj,
@@ -198,27 +138,22 @@ __global__ __launch_bounds__(WBLOCK) void pack_cols_k(const int *__restrict__ rp
 
 int strength_dev(hipStream_t s, const DCsr &A, double theta, double max_row_sum, int nfun, DCsr &S)
 {
-   unsigned char *d_keep = nullptr;
-   int *d_cnt = nullptr;
+   DBuf<unsigned char> d_keep;
+   DBuf<int> d_cnt;
+   std::vector<int> rp;
    S = DCsr();
    S.n = S.m = A.n;
-   auto run = [&]() -> int {
-      AMG_TRY(dalloc(&d_keep, (size_t)A.nnz));
-      AMG_TRY(dalloc(&d_cnt, (size_t)A.n));
-      strength_flag_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.v, A.n, theta, max_row_sum, nfun, d_keep, d_cnt);
-      AMG_HIP(hipGetLastError());
-      AMG_TRY(scan_counts(s, d_cnt, A.n, &S.rp, &S.nnz));
-      AMG_TRY(dalloc(&S.cj, (size_t)S.nnz));
-      pack_cols_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.n, d_keep, S.rp, S.cj);
-      AMG_HIP(hipGetLastError());
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   hipFree(d_keep), hipFree(d_cnt);
-   if (st != AMG_OK) S.release();
-   return st;
+   AMG_TRY(d_keep.alloc((size_t)A.nnz));
+   AMG_TRY(d_cnt.alloc((size_t)A.n));
+   strength_flag_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.v, A.n, theta, max_row_sum, nfun, d_keep, d_cnt);
+   AMG_HIP(hipGetLastError());
+   AMG_TRY(rowptr_of_counts(s, d_cnt, A.n, rp, S.rp));
+   S.nnz = rp[A.n];
+   AMG_TRY(S.cj.alloc((size_t)S.nnz));
+   pack_cols_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.n, d_keep, S.rp, S.cj);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipStreamSynchronize(s)); // rp leaves scope
+   return AMG_OK;
 }
 
 // ---- transpose ------------------------------------------------------------------
@@ -265,44 +200,31 @@ __global__ __launch_bounds__(WBLOCK) void tr_place_k(const int *__restrict__ trp
 
 int transpose_dev(hipStream_t s, const DCsr &A, bool values, DCsr &T)
 {
-   int *d_cnt = nullptr, *d_pos = nullptr;
-   long long *d_key = nullptr;
+   DBuf<int> d_cnt, d_pos;
+   DBuf<long long> d_key;
+   std::vector<int> trp;
    T = DCsr();
    T.n = A.m, T.m = A.n;
-   auto run = [&]() -> int {
-      AMG_TRY(dalloc(&d_cnt, (size_t)A.m));
-      AMG_HIP(hipMemsetAsync(d_cnt, 0, std::max<size_t>(A.m, 1) * sizeof(int), s));
-      if (A.nnz) tr_count_k<<<(unsigned)((A.nnz + 255) / 256), 256, 0, s>>>(A.cj, A.nnz, d_cnt);
-      AMG_HIP(hipGetLastError());
-      AMG_TRY(scan_counts(s, d_cnt, A.m, &T.rp, &T.nnz));
-      AMG_TRY(dalloc(&d_pos, (size_t)A.m));
-      if (A.m) AMG_HIP(hipMemcpyAsync(d_pos, T.rp, (size_t)A.m * sizeof(int), hipMemcpyDeviceToDevice, s));
-      AMG_TRY(dalloc(&d_key, (size_t)A.nnz));
-      AMG_TRY(dalloc(&T.cj, (size_t)A.nnz));
-      if (values) AMG_TRY(dalloc(&T.v, (size_t)A.nnz));
-      if (A.n) tr_fill_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.n, d_pos, d_key);
-      AMG_HIP(hipGetLastError());
-      if (A.m) tr_place_k<<<wave_grid(A.m), WBLOCK, 0, s>>>(T.rp, d_key, A.m, A.rp, A.v, T.cj, values ? T.v : nullptr);
-      AMG_HIP(hipGetLastError());
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   hipFree(d_cnt), hipFree(d_pos), hipFree(d_key);
-   if (st != AMG_OK) T.release();
-   return st;
+   AMG_TRY(d_cnt.alloc((size_t)A.m));
+   AMG_HIP(hipMemsetAsync(d_cnt, 0, std::max<size_t>(A.m, 1) * sizeof(int), s));
+   if (A.nnz) tr_count_k<<<(unsigned)((A.nnz + 255) / 256), 256, 0, s>>>(A.cj, A.nnz, d_cnt);
+   AMG_HIP(hipGetLastError());
+   AMG_TRY(rowptr_of_counts(s, d_cnt, A.m, trp, T.rp));
+   T.nnz = trp[A.m];
+   AMG_TRY(d_pos.alloc((size_t)A.m));
+   if (A.m) AMG_HIP(hipMemcpyAsync(d_pos, T.rp, (size_t)A.m * sizeof(int), hipMemcpyDeviceToDevice, s));
+   AMG_TRY(d_key.alloc((size_t)A.nnz));
+   AMG_TRY(T.cj.alloc((size_t)A.nnz));
+   if (values) AMG_TRY(T.v.alloc((size_t)A.nnz));
+   if (A.n) tr_fill_k<<<wave_grid(A.n), WBLOCK, 0, s>>>(A.rp, A.cj, A.n, d_pos, d_key);
+   AMG_HIP(hipGetLastError());
+   if (A.m) tr_place_k<<<wave_grid(A.m), WBLOCK, 0, s>>>(T.rp, d_key, A.m, A.rp, A.v, T.cj, T.v);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipStreamSynchronize(s)); // trp leaves scope
+   return AMG_OK;
 }
 
 // ---- PMIS -----------------------------------------------------------------------
-__device__ inline unsigned long long splitmix64_d(unsigned long long x)
-{
-   x += 0x9e3779b97f4a7c15ULL;
-   x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-   x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-   return x ^ (x >> 31);
-}
-
 // ctr[1] += the points left undecided
 __global__ void pmis_init_k(const int *__restrict__ strp, int n, unsigned long long seed, double *__restrict__ meas,
                             int *__restrict__ cf, int *__restrict__ ctr)
@@ -311,7 +233,7 @@ __global__ void pmis_init_k(const int *__restrict__ strp, int n, unsigned long l
    bool und = false;
    if (i < n) {
       const double r =
-         (double)(splitmix64_d(seed ^ (unsigned long long)i * 0x2545f4914f6cdd1dULL) >> 11) * 0x1.0p-53;
+         (double)(splitmix64(seed ^ (unsigned long long)i * 0x2545f4914f6cdd1dULL) >> 11) * 0x1.0p-53;
       const double ms = (strp[i + 1] - strp[i]) + r;
       meas[i] = ms;
       und = !(ms < 1.0);
@@ -382,44 +304,38 @@ __global__ void pmis_rest_k(int n, int *__restrict__ cf)
 int pmis_dev(hipStream_t s, const DCsr &S, const DCsr &ST, unsigned long long seed, int *d_cf, int *rounds_out)
 {
    const int n = S.n;
-   double *d_meas = nullptr;
-   unsigned char *d_newc = nullptr;
-   int *d_ctr = nullptr;
-   auto run = [&]() -> int {
-      AMG_TRY(dalloc(&d_meas, (size_t)n));
-      AMG_TRY(dalloc(&d_newc, (size_t)n));
-      AMG_TRY(dalloc(&d_ctr, 2));
-      const int grid = (n + 255) / 256;
-      int ctr[2] = {0, 0};
+   DBuf<double> d_meas;
+   DBuf<unsigned char> d_newc;
+   DBuf<int> d_ctr;
+   AMG_TRY(d_meas.alloc((size_t)n));
+   AMG_TRY(d_newc.alloc((size_t)n));
+   AMG_TRY(d_ctr.alloc(2));
+   const int grid = (n + 255) / 256;
+   int ctr[2] = {0, 0};
+   AMG_HIP(hipMemsetAsync(d_ctr, 0, 2 * sizeof(int), s));
+   pmis_init_k<<<grid, 256, 0, s>>>(ST.rp, n, seed, d_meas, d_cf, d_ctr);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipMemcpyAsync(ctr, d_ctr, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+   AMG_HIP(hipStreamSynchronize(s));
+   long long left = ctr[1];
+   int rounds = 0;
+   // a round decides at least one point or ends the loop; n + 1 is a hard cap
+   for (long long it = 0; left > 0 && it <= n; it++) {
       AMG_HIP(hipMemsetAsync(d_ctr, 0, 2 * sizeof(int), s));
-      pmis_init_k<<<grid, 256, 0, s>>>(ST.rp, n, seed, d_meas, d_cf, d_ctr);
+      pmis_select_k<<<grid, 256, 0, s>>>(S.rp, S.cj, ST.rp, ST.cj, n, d_cf, d_meas, d_newc, d_ctr);
+      pmis_apply_k<<<grid, 256, 0, s>>>(S.rp, S.cj, n, d_newc, d_cf, d_ctr);
       AMG_HIP(hipGetLastError());
       AMG_HIP(hipMemcpyAsync(ctr, d_ctr, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
       AMG_HIP(hipStreamSynchronize(s));
-      long long left = ctr[1];
-      int rounds = 0;
-      // a round decides at least one point or ends the loop; n + 1 is a hard cap
-      for (long long it = 0; left > 0 && it <= n; it++) {
-         AMG_HIP(hipMemsetAsync(d_ctr, 0, 2 * sizeof(int), s));
-         pmis_select_k<<<grid, 256, 0, s>>>(S.rp, S.cj, ST.rp, ST.cj, n, d_cf, d_meas, d_newc, d_ctr);
-         pmis_apply_k<<<grid, 256, 0, s>>>(S.rp, S.cj, n, d_newc, d_cf, d_ctr);
-         AMG_HIP(hipGetLastError());
-         AMG_HIP(hipMemcpyAsync(ctr, d_ctr, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-         AMG_HIP(hipStreamSynchronize(s));
-         if (ctr[0] == 0) break; // the host's `break`: the rest become F
-         left -= ctr[1];
-         rounds++;
-      }
-      pmis_rest_k<<<grid, 256, 0, s>>>(n, d_cf);
-      AMG_HIP(hipGetLastError());
-      AMG_HIP(hipStreamSynchronize(s));
-      if (rounds_out) *rounds_out = rounds;
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   hipFree(d_meas), hipFree(d_newc), hipFree(d_ctr);
-   return st;
+      if (ctr[0] == 0) break; // the host's `break`: the rest become F
+      left -= ctr[1];
+      rounds++;
+   }
+   pmis_rest_k<<<grid, 256, 0, s>>>(n, d_cf);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipStreamSynchronize(s));
+   if (rounds_out) *rounds_out = rounds;
+   return AMG_OK;
 }
 
 // ---- interpolation --------------------------------------------------------------
@@ -715,154 +631,89 @@ int interp_dev(hipStream_t s, const DCsr &A, const DCsr &S, const int *d_cf, con
                int nfun, DCsr &P)
 {
    const int n = A.n;
-   int *d_cidx = nullptr, *d_cand = nullptr, *d_chat = nullptr, *d_cnt = nullptr;
-   long long *d_ub = nullptr, *d_hoff = nullptr, *d_ooff = nullptr;
-   double *d_num = nullptr;
+   DBuf<int> d_cidx, d_cand, d_chat, d_cnt;
+   DBuf<long long> d_ub, d_hoff, d_ooff;
+   DBuf<double> d_num;
    struct Part {
-      int *cj;
-      double *v;
-      long long nz;
+      DBuf<int> cj;
+      DBuf<double> v;
+      long long nz = 0;
    };
    std::vector<Part> parts;
    P = DCsr();
-   auto run = [&]() -> int {
-      std::vector<int> cidx(n, -1);
-      int nc = 0;
-      for (int i = 0; i < n; i++)
-         if (cf[i] == CF_C) cidx[i] = nc++;
-      P.n = n, P.m = nc;
-      AMG_TRY(dput(s, cidx.data(), (size_t)n, &d_cidx));
-      AMG_TRY(dalloc(&d_ub, (size_t)n));
-      interp_ub_k<<<(n + 255) / 256, 256, 0, s>>>(S.rp, S.cj, d_cf, n, type, d_ub);
-      AMG_HIP(hipGetLastError());
-      std::vector<long long> ub;
-      AMG_TRY(dget(s, d_ub, (size_t)n, ub));
-      AMG_HIP(hipStreamSynchronize(s));
-      const long long budget = g_setup_budget.load();
-      auto batch_end = [&](int r0, long long *tot) {
-         long long t = 0;
-         int r1 = r0;
-         while (r1 < n && (r1 == r0 || t + ub[r1] <= budget)) t += ub[r1++];
-         *tot = t;
-         return r1;
-      };
-      long long maxb = 1;
-      int maxr = 1;
-      for (int r0 = 0; r0 < n;) {
-         long long tot;
-         const int r1 = batch_end(r0, &tot);
-         maxb = std::max(maxb, tot);
-         maxr = std::max(maxr, r1 - r0);
-         r0 = r1;
-      }
-      AMG_TRY(dalloc(&d_cand, (size_t)maxb));
-      AMG_TRY(dalloc(&d_chat, (size_t)maxb));
-      AMG_TRY(dalloc(&d_num, (size_t)maxb));
-      AMG_TRY(dalloc(&d_hoff, (size_t)maxr + 1));
-      AMG_TRY(dalloc(&d_ooff, (size_t)maxr + 1));
-      AMG_TRY(dalloc(&d_cnt, (size_t)maxr));
-      std::vector<int> prp((size_t)n + 1, 0);
-      long long used = 0;
-      for (int r0 = 0; r0 < n;) {
-         long long tot;
-         const int r1 = batch_end(r0, &tot), nr = r1 - r0;
-         std::vector<long long> hoff((size_t)nr + 1, 0), ooff((size_t)nr + 1, 0);
-         for (int q = 0; q < nr; q++) hoff[q + 1] = hoff[q] + ub[r0 + q];
-         AMG_HIP(hipMemcpyAsync(d_hoff, hoff.data(), ((size_t)nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-         interp_row_k<<<nr, 64, 0, s>>>(A.rp, A.cj, A.v, S.rp, S.cj, d_cf, d_cidx, r0, nr, d_hoff, d_cand, d_chat,
-                                        d_num, d_cnt, type, nfun);
-         AMG_HIP(hipGetLastError());
-         std::vector<int> cnt;
-         AMG_TRY(dget(s, d_cnt, (size_t)nr, cnt));
-         AMG_HIP(hipStreamSynchronize(s));
-         for (int q = 0; q < nr; q++) ooff[q + 1] = ooff[q] + cnt[q];
-         if (used + ooff[nr] > INT_MAX)
-            return amg_set_error(AMG_ERR_ARG, "classical setup on the device: P has more than 2^31 - 1 entries");
-         Part pt{nullptr, nullptr, ooff[nr]};
-         AMG_TRY(dalloc(&pt.cj, (size_t)pt.nz));
-         parts.push_back(pt);
-         AMG_TRY(dalloc(&parts.back().v, (size_t)pt.nz));
-         AMG_HIP(hipMemcpyAsync(d_ooff, ooff.data(), ((size_t)nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-         interp_pack_k<<<nr, 64, 0, s>>>(d_cf, d_cidx, r0, nr, d_hoff, d_chat, d_num, d_ooff, parts.back().cj,
-                                         parts.back().v);
-         AMG_HIP(hipGetLastError());
-         AMG_HIP(hipStreamSynchronize(s)); // hoff / ooff leave scope, the scratch is reused
-         for (int q = 0; q < nr; q++) prp[r0 + q + 1] = prp[r0 + q] + cnt[q];
-         used += ooff[nr];
-         r0 = r1;
-      }
-      P.nnz = used;
-      AMG_TRY(dput(s, prp.data(), (size_t)n + 1, &P.rp));
-      if (parts.size() == 1) { // one batch: its output is P
-         P.cj = parts[0].cj, P.v = parts[0].v;
-         parts.clear();
-      } else {
-         AMG_TRY(dalloc(&P.cj, (size_t)used));
-         AMG_TRY(dalloc(&P.v, (size_t)used));
-         long long o = 0;
-         for (const Part &pt : parts) {
-            if (pt.nz) {
-               AMG_HIP(hipMemcpyAsync(P.cj + o, pt.cj, (size_t)pt.nz * sizeof(int), hipMemcpyDeviceToDevice, s));
-               AMG_HIP(hipMemcpyAsync(P.v + o, pt.v, (size_t)pt.nz * sizeof(double), hipMemcpyDeviceToDevice, s));
-            }
-            o += pt.nz;
-         }
-      }
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (const Part &pt : parts) hipFree(pt.cj), hipFree(pt.v);
-   for (void *p : {(void *)d_cidx, (void *)d_cand, (void *)d_chat, (void *)d_cnt, (void *)d_ub, (void *)d_hoff,
-                   (void *)d_ooff, (void *)d_num})
-      hipFree(p);
-   if (st != AMG_OK) P.release();
-   return st;
-}
-
-// ---- host CSR in and out --------------------------------------------------------
-int upload_csr(hipStream_t s, int n, int m, const int *rp, const int *cj, const double *v, DCsr &D)
-{
-   D = DCsr();
-   D.n = n, D.m = m, D.nnz = rp[n];
-   AMG_TRY(dput(s, rp, (size_t)n + 1, &D.rp));
-   AMG_TRY(dput(s, cj, (size_t)D.nnz, &D.cj));
-   if (v) AMG_TRY(dput(s, v, (size_t)D.nnz, &D.v));
-   return AMG_OK;
-}
-
-int download_csr(hipStream_t s, const DCsr &D, bool values, std::vector<int> &rp, std::vector<int> &cj,
-                 std::vector<double> &v)
-{
-   AMG_TRY(dget(s, D.rp, (size_t)D.n + 1, rp));
-   AMG_TRY(dget(s, D.cj, (size_t)D.nnz, cj));
-   if (values)
-      AMG_TRY(dget(s, D.v, (size_t)D.nnz, v));
-   else
-      v.clear();
+   std::vector<int> cidx(n, -1);
+   int nc = 0;
+   for (int i = 0; i < n; i++)
+      if (cf[i] == CF_C) cidx[i] = nc++;
+   P.n = n, P.m = nc;
+   AMG_TRY(upload(s, cidx.data(), (size_t)n, d_cidx));
+   AMG_TRY(d_ub.alloc((size_t)n));
+   interp_ub_k<<<(n + 255) / 256, 256, 0, s>>>(S.rp, S.cj, d_cf, n, type, d_ub);
+   AMG_HIP(hipGetLastError());
+   std::vector<long long> ub;
+   AMG_TRY(download(s, d_ub.p, (size_t)n, ub));
    AMG_HIP(hipStreamSynchronize(s));
-   return AMG_OK;
-}
-
-// the device selected and a stream of the call's own
-struct Session {
-   hipStream_t s = nullptr;
-   int open(int device)
-   {
-      AMG_HIP(hipSetDevice(device));
-      AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-      return AMG_OK;
+   const std::vector<int> cut = batch_bounds(ub, g_setup_budget.load());
+   long long maxb = 1;
+   int maxr = 1;
+   for (size_t b = 0; b + 1 < cut.size(); b++) {
+      maxb = std::max(maxb, std::accumulate(ub.begin() + cut[b], ub.begin() + cut[b + 1], 0LL));
+      maxr = std::max(maxr, cut[b + 1] - cut[b]);
    }
-   void close()
-   {
-      if (s) {
-         hipStreamSynchronize(s);
-         hipStreamDestroy(s);
-         s = nullptr;
+   AMG_TRY(d_cand.alloc((size_t)maxb));
+   AMG_TRY(d_chat.alloc((size_t)maxb));
+   AMG_TRY(d_num.alloc((size_t)maxb));
+   AMG_TRY(d_hoff.alloc((size_t)maxr + 1));
+   AMG_TRY(d_ooff.alloc((size_t)maxr + 1));
+   AMG_TRY(d_cnt.alloc((size_t)maxr));
+   std::vector<int> prp((size_t)n + 1, 0);
+   long long used = 0;
+   for (size_t b = 0; b + 1 < cut.size(); b++) {
+      const int r0 = cut[b], nr = cut[b + 1] - r0;
+      std::vector<long long> hoff((size_t)nr + 1, 0), ooff((size_t)nr + 1, 0);
+      for (int q = 0; q < nr; q++) hoff[q + 1] = hoff[q] + ub[r0 + q];
+      AMG_HIP(hipMemcpyAsync(d_hoff, hoff.data(), ((size_t)nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+      interp_row_k<<<nr, 64, 0, s>>>(A.rp, A.cj, A.v, S.rp, S.cj, d_cf, d_cidx, r0, nr, d_hoff, d_cand, d_chat, d_num,
+                                     d_cnt, type, nfun);
+      AMG_HIP(hipGetLastError());
+      std::vector<int> cnt;
+      AMG_TRY(download(s, d_cnt.p, (size_t)nr, cnt));
+      AMG_HIP(hipStreamSynchronize(s));
+      for (int q = 0; q < nr; q++) ooff[q + 1] = ooff[q] + cnt[q];
+      if (used + ooff[nr] > INT_MAX)
+         return amg_set_error(AMG_ERR_ARG, "classical setup on the device: P has more than 2^31 - 1 entries");
+      parts.emplace_back();
+      Part &pt = parts.back();
+      pt.nz = ooff[nr];
+      AMG_TRY(pt.cj.alloc((size_t)pt.nz));
+      AMG_TRY(pt.v.alloc((size_t)pt.nz));
+      AMG_HIP(hipMemcpyAsync(d_ooff, ooff.data(), ((size_t)nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+      interp_pack_k<<<nr, 64, 0, s>>>(d_cf, d_cidx, r0, nr, d_hoff, d_chat, d_num, d_ooff, pt.cj, pt.v);
+      AMG_HIP(hipGetLastError());
+      AMG_HIP(hipStreamSynchronize(s)); // hoff / ooff leave scope, the scratch is reused
+      AMG_TRY(scan_counts(cnt.data(), nr, &prp[r0]));
+      used += ooff[nr];
+   }
+   P.nnz = used;
+   AMG_TRY(upload(s, prp.data(), (size_t)n + 1, P.rp));
+   if (parts.size() == 1) { // one batch: its output is P
+      P.cj = std::move(parts[0].cj);
+      P.v = std::move(parts[0].v);
+   } else {
+      AMG_TRY(P.cj.alloc((size_t)used));
+      AMG_TRY(P.v.alloc((size_t)used));
+      long long o = 0;
+      for (const Part &pt : parts) {
+         if (pt.nz) {
+            AMG_HIP(hipMemcpyAsync(P.cj.p + o, pt.cj, (size_t)pt.nz * sizeof(int), hipMemcpyDeviceToDevice, s));
+            AMG_HIP(hipMemcpyAsync(P.v.p + o, pt.v, (size_t)pt.nz * sizeof(double), hipMemcpyDeviceToDevice, s));
+         }
+         o += pt.nz;
       }
    }
-};
+   AMG_HIP(hipStreamSynchronize(s)); // prp and cidx leave scope
+   return AMG_OK;
+}
 
 } // namespace
 
@@ -873,89 +724,60 @@ extern "C" int amg_set_setup_scratch(long long slots)
    return AMG_OK;
 }
 
-int amg_strength_device(int device, int n, const int *rp, const int *cj, const double *v, double theta,
-                        double max_row_sum, int nfun, std::vector<int> &srp, std::vector<int> &scj)
+// ---- host CSR in and out --------------------------------------------------------
+int amg_strength_device(int device, const HCsrView &A, double theta, double max_row_sum, int nfun, HCsr &S)
 {
    Session ss;
    AMG_TRY(ss.open(device));
-   DCsr A, S;
-   std::vector<double> none;
-   auto run = [&]() -> int {
-      AMG_TRY(upload_csr(ss.s, n, n, rp, cj, v, A));
-      AMG_TRY(strength_dev(ss.s, A, theta, max_row_sum, nfun, S));
-      return download_csr(ss.s, S, false, srp, scj, none);
-   };
-   const int st = run();
-   hipStreamSynchronize(ss.s);
-   A.release(), S.release();
-   ss.close();
-   return st;
+   DCsr dA, dS;
+   AMG_TRY(upload_csr(ss.s, A, true, dA));
+   AMG_TRY(strength_dev(ss.s, dA, theta, max_row_sum, nfun, dS));
+   AMG_TRY(download_csr(ss.s, dS, false, S));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
 
-int amg_transpose_device(int device, int n, int m, const int *rp, const int *cj, const double *v_or_null,
-                         std::vector<int> &trp, std::vector<int> &tcj, std::vector<double> &tv)
+int amg_transpose_device(int device, const HCsrView &A, HCsr &T)
 {
    Session ss;
    AMG_TRY(ss.open(device));
-   DCsr A, T;
-   auto run = [&]() -> int {
-      AMG_TRY(upload_csr(ss.s, n, m, rp, cj, v_or_null, A));
-      AMG_TRY(transpose_dev(ss.s, A, v_or_null != nullptr, T));
-      return download_csr(ss.s, T, v_or_null != nullptr, trp, tcj, tv);
-   };
-   const int st = run();
-   hipStreamSynchronize(ss.s);
-   A.release(), T.release();
-   ss.close();
-   return st;
+   DCsr dA, dT;
+   AMG_TRY(upload_csr(ss.s, A, A.v != nullptr, dA));
+   AMG_TRY(transpose_dev(ss.s, dA, A.v != nullptr, dT));
+   AMG_TRY(download_csr(ss.s, dT, A.v != nullptr, T));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
 
-int amg_pmis_device(int device, int n, const int *srp, const int *scj, unsigned long long seed, int *cf, int *rounds)
+int amg_pmis_device(int device, const HCsrView &S, unsigned long long seed, int *cf, int *rounds)
 {
    Session ss;
    AMG_TRY(ss.open(device));
-   DCsr S, ST;
-   int *d_cf = nullptr;
-   auto run = [&]() -> int {
-      AMG_TRY(upload_csr(ss.s, n, n, srp, scj, nullptr, S));
-      AMG_TRY(transpose_dev(ss.s, S, false, ST));
-      AMG_TRY(dalloc(&d_cf, (size_t)n));
-      AMG_TRY(pmis_dev(ss.s, S, ST, seed, d_cf, rounds));
-      AMG_HIP(hipMemcpyAsync(cf, d_cf, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ss.s));
-      AMG_HIP(hipStreamSynchronize(ss.s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(ss.s);
-   S.release(), ST.release();
-   hipFree(d_cf);
-   ss.close();
-   return st;
+   DCsr dS, dST;
+   DBuf<int> d_cf;
+   AMG_TRY(upload_csr(ss.s, S, false, dS));
+   AMG_TRY(transpose_dev(ss.s, dS, false, dST));
+   AMG_TRY(d_cf.alloc((size_t)S.n));
+   AMG_TRY(pmis_dev(ss.s, dS, dST, seed, d_cf, rounds));
+   AMG_HIP(hipMemcpyAsync(cf, d_cf, (size_t)S.n * sizeof(int), hipMemcpyDeviceToHost, ss.s));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
 
-int amg_interp_device(int device, int n, const int *rp, const int *cj, const double *v, const int *srp, const int *scj,
-                      const int *cf, int type, int nfun, int *nc, std::vector<int> &prp, std::vector<int> &pcj,
-                      std::vector<double> &pv)
+int amg_interp_device(int device, const HCsrView &A, const HCsrView &S, const int *cf, int type, int nfun, HCsr &P)
 {
    Session ss;
    AMG_TRY(ss.open(device));
-   DCsr A, S, P;
-   int *d_cf = nullptr;
-   auto run = [&]() -> int {
-      AMG_TRY(upload_csr(ss.s, n, n, rp, cj, v, A));
-      AMG_TRY(upload_csr(ss.s, n, n, srp, scj, nullptr, S));
-      AMG_TRY(dput(ss.s, cf, (size_t)n, &d_cf));
-      const std::vector<int> hcf(cf, cf + n);
-      AMG_TRY(interp_dev(ss.s, A, S, d_cf, hcf, type, nfun, P));
-      *nc = P.m;
-      return download_csr(ss.s, P, true, prp, pcj, pv);
-   };
-   const int st = run();
-   hipStreamSynchronize(ss.s);
-   A.release(), S.release(), P.release();
-   hipFree(d_cf);
-   ss.close();
-   return st;
+   DCsr dA, dS, dP;
+   DBuf<int> d_cf;
+   AMG_TRY(upload_csr(ss.s, A, true, dA));
+   AMG_TRY(upload_csr(ss.s, S, false, dS));
+   AMG_TRY(upload(ss.s, cf, (size_t)A.n, d_cf));
+   const std::vector<int> hcf(cf, cf + A.n);
+   AMG_TRY(interp_dev(ss.s, dA, dS, d_cf, hcf, type, nfun, dP));
+   AMG_TRY(download_csr(ss.s, dP, true, P));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
 
 // The level loop of amg_classical_setup with the hierarchy resident on the
@@ -963,91 +785,79 @@ int amg_interp_device(int device, int n, const int *rp, const int *cj, const dou
 // A_{l+1} stays there as the next level's input, and a level's cf, P, R and
 // A_{l+1} are what is downloaded.  HMIS coarsens on the host (hmis: S in, cf
 // out).  Stall and stop rules as on the host.
-int amg_classical_setup_device(const amg_classical_opts *o, int n, const int *rp, const int *cj, const double *v,
-                               const amg_hmis_fn &hmis, std::vector<amg_setup_dev_level> &levels)
+int amg_classical_setup_device(const amg_classical_opts *o, const HCsr &A0, const amg_hmis_fn &hmis,
+                               std::vector<amg_setup_dev_level> &levels)
 {
    Session ss;
    AMG_TRY(ss.open(o->device));
    hipStream_t s = ss.s;
    DCsr A, S, ST, P, R, AP, Ac;
-   int *d_cf = nullptr;
+   DBuf<int> d_cf;
    const bool tm = std::getenv("AMG_CLASSICAL_TIMING") != nullptr;
    auto now = [&] {
       hipStreamSynchronize(s);
       return std::chrono::steady_clock::now();
    };
    const uint64_t seed = o->coarsen_type == AMG_COARSEN_PMIS ? o->seed + 0x9e37ULL : o->seed;
-   auto run = [&]() -> int {
-      AMG_TRY(upload_csr(s, n, n, rp, cj, v, A));
-      for (int l = 0; l + 1 < o->max_levels; l++) {
-         if (A.n <= o->max_coarse_size) break;
-         const int nfun = A.n % o->num_functions == 0 ? o->num_functions : 1;
-         auto t0 = now();
-         AMG_TRY(strength_dev(s, A, o->strong_threshold, o->max_row_sum, nfun, S));
-         amg_setup_dev_level L;
-         AMG_TRY(dalloc(&d_cf, (size_t)A.n));
-         std::chrono::steady_clock::time_point t1;
-         int rounds = 0;
-         if (o->coarsen_type == AMG_COARSEN_HMIS) {
-            t1 = now();
-            std::vector<int> srp, scj;
-            std::vector<double> none;
-            AMG_TRY(download_csr(s, S, false, srp, scj, none));
-            hmis(A.n, srp, scj, L.cf);
-            AMG_HIP(hipMemcpyAsync(d_cf, L.cf.data(), (size_t)A.n * sizeof(int), hipMemcpyHostToDevice, s));
-         } else {
-            AMG_TRY(transpose_dev(s, S, false, ST));
-            t1 = now();
-            AMG_TRY(pmis_dev(s, S, ST, seed + (uint64_t)l * 7919ULL, d_cf, &rounds));
-            AMG_TRY(dget(s, d_cf, (size_t)A.n, L.cf));
-            ST.release();
-         }
-         auto t2 = now();
-         int nc = 0;
-         for (int c : L.cf) nc += c == CF_C;
-         if (nc == 0 || nc == A.n) break; // coarsening stalled
-         AMG_TRY(interp_dev(s, A, S, d_cf, L.cf, o->interp_type, nfun, P));
-         S.release();
-         hipFree(d_cf), d_cf = nullptr;
-         auto t3 = now();
-         if (o->P_max_elmts > 0 || o->trunc_factor > 0.0) {
-            DCsr T;
-            T.n = P.n, T.m = P.m;
-            AMG_TRY(amg_trunc_dev(s, P.n, P.rp, P.cj, P.v, P.nnz, o->trunc_factor, o->P_max_elmts, &T.rp, &T.cj, &T.v,
-                                  &T.nnz));
-            P.release();
-            P = T;
-         }
-         AMG_TRY(transpose_dev(s, P, true, R));
-         AP.n = A.n, AP.m = P.m;
-         AMG_TRY(amg_spgemm_dev(s, A.n, A.rp, A.cj, A.v, P.rp, P.cj, P.v, P.m, &AP.rp, &AP.cj, &AP.v, &AP.nnz));
-         A.release(); // A_l is on the host already: make room for the second product
-         Ac.n = Ac.m = P.m;
-         AMG_TRY(amg_spgemm_dev(s, R.n, R.rp, R.cj, R.v, AP.rp, AP.cj, AP.v, P.m, &Ac.rp, &Ac.cj, &Ac.v, &Ac.nnz));
-         AP.release();
-         L.n = P.n, L.nc = P.m;
-         AMG_TRY(download_csr(s, P, true, L.prp, L.pcj, L.pv));
-         AMG_TRY(download_csr(s, R, true, L.rrp, L.rcj, L.rv));
-         AMG_TRY(download_csr(s, Ac, true, L.arp, L.acj, L.av));
-         P.release(), R.release();
-         A = Ac;
-         Ac = DCsr();
-         auto t4 = now();
-         if (tm) {
-            auto d = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
-            std::fprintf(stderr,
-                         "[classical] level %d n=%d: strength %.3fs coarsen %.3fs interp %.3fs RAP %.3fs "
-                         "(device, %d PMIS rounds)\n",
-                         l, L.n, d(t0, t1), d(t1, t2), d(t2, t3), d(t3, t4), rounds);
-         }
-         levels.push_back(std::move(L));
+   AMG_TRY(upload_csr(s, view(A0), true, A));
+   for (int l = 0; l + 1 < o->max_levels; l++) {
+      if (A.n <= o->max_coarse_size) break;
+      const int nfun = A.n % o->num_functions == 0 ? o->num_functions : 1;
+      auto t0 = now();
+      AMG_TRY(strength_dev(s, A, o->strong_threshold, o->max_row_sum, nfun, S));
+      amg_setup_dev_level L;
+      AMG_TRY(d_cf.alloc((size_t)A.n));
+      std::chrono::steady_clock::time_point t1;
+      int rounds = 0;
+      if (o->coarsen_type == AMG_COARSEN_HMIS) {
+         t1 = now();
+         HCsr Sh;
+         AMG_TRY(download_csr(s, S, false, Sh));
+         AMG_HIP(hipStreamSynchronize(s));
+         hmis(Sh, L.cf);
+         AMG_HIP(hipMemcpyAsync(d_cf, L.cf.data(), (size_t)A.n * sizeof(int), hipMemcpyHostToDevice, s));
+      } else {
+         AMG_TRY(transpose_dev(s, S, false, ST));
+         t1 = now();
+         AMG_TRY(pmis_dev(s, S, ST, seed + (uint64_t)l * 7919ULL, d_cf, &rounds));
+         AMG_TRY(download(s, d_cf.p, (size_t)A.n, L.cf));
+         ST.release();
       }
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (DCsr *M : {&A, &S, &ST, &P, &R, &AP, &Ac}) M->release();
-   hipFree(d_cf);
-   ss.close();
-   return st;
+      auto t2 = now();
+      int nc = 0;
+      for (int c : L.cf) nc += c == CF_C;
+      if (nc == 0 || nc == A.n) break; // coarsening stalled
+      AMG_TRY(interp_dev(s, A, S, d_cf, L.cf, o->interp_type, nfun, P));
+      S.release();
+      d_cf.release();
+      auto t3 = now();
+      if (o->P_max_elmts > 0 || o->trunc_factor > 0.0) {
+         DCsr T;
+         AMG_TRY(trunc_dev(s, P, o->trunc_factor, o->P_max_elmts, T));
+         P = std::move(T);
+      }
+      AMG_TRY(transpose_dev(s, P, true, R));
+      AMG_TRY(spgemm_dev(s, A, P, AP));
+      A.release(); // A_l is on the host already: make room for the second product
+      AMG_TRY(spgemm_dev(s, R, AP, Ac));
+      AP.release();
+      AMG_TRY(download_csr(s, P, true, L.P));
+      AMG_HIP(hipStreamSynchronize(s));
+      AMG_TRY(download_csr(s, R, true, L.R));
+      AMG_HIP(hipStreamSynchronize(s));
+      AMG_TRY(download_csr(s, Ac, true, L.Ac));
+      AMG_HIP(hipStreamSynchronize(s));
+      P.release(), R.release();
+      A = std::move(Ac);
+      auto t4 = now();
+      if (tm) {
+         auto d = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
+         std::fprintf(stderr,
+                      "[classical] level %d n=%d: strength %.3fs coarsen %.3fs interp %.3fs RAP %.3fs "
+                      "(device, %d PMIS rounds)\n",
+                      l, L.P.n, d(t0, t1), d(t1, t2), d(t2, t3), d(t3, t4), rounds);
+      }
+      levels.push_back(std::move(L));
+   }
+   return AMG_OK;
 }

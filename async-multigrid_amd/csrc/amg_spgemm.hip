@@ -13,12 +13,14 @@
 // square products, and rows packed by an exclusive scan of their counts.  Rows
 // run in batches sized to a scratch budget (upper bound per row: the sum of
 // the B rows its A entries name).
+// spgemm_dev works on device CSRs (amg_csr.h's DCsr); the amg_*_device entry
+// points below it take host CSRs through a stream of their own.
 #include <algorithm>
 #include <atomic>
 #include <numeric>
 #include <vector>
 
-#include "amg_internal.h"
+#include "amg_csr.h"
 
 namespace {
 
@@ -121,150 +123,91 @@ __global__ void spgemm_pack_k(const long long *__restrict__ hoff, const int *__r
    }
 }
 
-template <class T>
-int dupload(hipStream_t s, const std::vector<T> &h, T **d)
-{
-   AMG_HIP(hipMalloc(d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-   if (!h.empty()) AMG_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-   return AMG_OK;
-}
-
-// C = A B with every operand on the device: A An x (B's rows), B with Bm
-// columns; C's rowptr / col / val allocated here (*d_crp, *d_ccj, *d_cv) and
-// its entry count in *nnz
-int spgemm_dev(hipStream_t s, int An, const int *d_arp, const int *d_acj, const double *d_av, const int *d_brp,
-               const int *d_bcj, const double *d_bv, int Bm, int **d_crp, int **d_ccj, double **d_cv, long long *nnz)
-{
-   long long *d_ub = nullptr, *d_hoff = nullptr, *d_ooff = nullptr;
-   int *d_hcol = nullptr, *d_cnt = nullptr, *d_ocol = nullptr;
-   double *d_hval = nullptr, *d_oval = nullptr;
-   int *c_col = nullptr;
-   double *c_val = nullptr;
-   long long c_cap = 0;
-   auto cleanup = [&]() {
-      hipStreamSynchronize(s);
-      for (void *p : {(void *)d_ub, (void *)d_hoff, (void *)d_ooff, (void *)d_hcol, (void *)d_cnt, (void *)d_ocol,
-                      (void *)d_hval, (void *)d_oval})
-         hipFree(p);
-   };
-   auto run = [&]() -> int {
-      AMG_HIP(hipMalloc(&d_ub, std::max(An, 1) * sizeof(long long)));
-      if (An > 0) spgemm_ub_k<<<(An + 255) / 256, 256, 0, s>>>(d_arp, d_acj, d_brp, An, d_ub);
-      std::vector<long long> ub(An);
-      if (An > 0) AMG_HIP(hipMemcpyAsync(ub.data(), d_ub, An * sizeof(long long), hipMemcpyDeviceToHost, s));
-      AMG_HIP(hipStreamSynchronize(s));
-      // table capacity per row: a power of two >= 2 ub (>= 2)
-      std::vector<long long> capr(An);
-      for (int r = 0; r < An; r++) {
-         long long c = 2;
-         while (c < 2 * ub[r]) c <<= 1;
-         capr[r] = c;
-      }
-      // batches of rows within the scratch budget (12 bytes per slot)
-      const long long budget = g_budget.load(); // slots: 6 GiB of scratch by default
-      long long maxb = 1;
-      for (int r0 = 0; r0 < An;) {
-         long long tot = 0;
-         int r1 = r0;
-         while (r1 < An && (r1 == r0 || tot + capr[r1] <= budget)) tot += capr[r1++];
-         maxb = std::max(maxb, tot);
-         r0 = r1;
-      }
-      AMG_HIP(hipMalloc(&d_hcol, maxb * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_hval, maxb * sizeof(double)));
-      AMG_HIP(hipMalloc(&d_hoff, (size_t)(An + 1) * sizeof(long long)));
-      AMG_HIP(hipMalloc(&d_ooff, (size_t)(An + 1) * sizeof(long long)));
-      AMG_HIP(hipMalloc(&d_cnt, std::max(An, 1) * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_ocol, maxb * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_oval, maxb * sizeof(double)));
-      std::vector<int> crp(An + 1, 0);
-      long long used = 0;
-      for (int r0 = 0; r0 < An;) {
-         long long tot = 0;
-         int r1 = r0;
-         while (r1 < An && (r1 == r0 || tot + capr[r1] <= budget)) tot += capr[r1++];
-         const int nr = r1 - r0;
-         std::vector<long long> hoff(nr + 1, 0);
-         for (int q = 0; q < nr; q++) hoff[q + 1] = hoff[q] + capr[r0 + q];
-         AMG_HIP(hipMemcpyAsync(d_hoff, hoff.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-         spgemm_row_k<<<(nr + 127) / 128, 128, 0, s>>>(d_arp, d_acj, d_av, d_brp, d_bcj, d_bv, r0, nr, d_hoff,
-                                                       d_hcol, d_hval, d_cnt, An == Bm ? 1 : 0);
-         AMG_HIP(hipGetLastError());
-         std::vector<int> cnt(nr);
-         AMG_HIP(hipMemcpyAsync(cnt.data(), d_cnt, nr * sizeof(int), hipMemcpyDeviceToHost, s));
-         AMG_HIP(hipStreamSynchronize(s));
-         std::vector<long long> ooff(nr + 1, 0);
-         for (int q = 0; q < nr; q++) ooff[q + 1] = ooff[q] + cnt[q];
-         AMG_HIP(hipMemcpyAsync(d_ooff, ooff.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-         spgemm_pack_k<<<nr, 64, 0, s>>>(d_hoff, d_hcol, d_hval, d_ooff, nr, d_ocol, d_oval);
-         // append the batch to C (grown by doubling, device to device)
-         if (used + ooff[nr] > c_cap) {
-            const long long cap = std::max(used + ooff[nr], 2 * c_cap);
-            int *nc = nullptr;
-            double *nv = nullptr;
-            AMG_HIP(hipMalloc(&nc, std::max(cap, 1LL) * sizeof(int)));
-            if (hipMalloc(&nv, std::max(cap, 1LL) * sizeof(double)) != hipSuccess) {
-               hipFree(nc);
-               return amg_set_error(AMG_ERR_OOM, "spgemm_dev: %lld entries", cap);
-            }
-            if (used) {
-               AMG_HIP(hipMemcpyAsync(nc, c_col, used * sizeof(int), hipMemcpyDeviceToDevice, s));
-               AMG_HIP(hipMemcpyAsync(nv, c_val, used * sizeof(double), hipMemcpyDeviceToDevice, s));
-            }
-            AMG_HIP(hipStreamSynchronize(s));
-            hipFree(c_col);
-            hipFree(c_val);
-            c_col = nc;
-            c_val = nv;
-            c_cap = cap;
-         }
-         if (ooff[nr]) {
-            AMG_HIP(hipMemcpyAsync(c_col + used, d_ocol, ooff[nr] * sizeof(int), hipMemcpyDeviceToDevice, s));
-            AMG_HIP(hipMemcpyAsync(c_val + used, d_oval, ooff[nr] * sizeof(double), hipMemcpyDeviceToDevice, s));
-         }
-         AMG_HIP(hipStreamSynchronize(s));
-         for (int q = 0; q < nr; q++) crp[r0 + q + 1] = crp[r0 + q] + cnt[q];
-         used += ooff[nr];
-         r0 = r1;
-      }
-      if (!c_col) {
-         AMG_HIP(hipMalloc(&c_col, sizeof(int)));
-         AMG_HIP(hipMalloc(&c_val, sizeof(double)));
-      }
-      int *rp = nullptr;
-      AMG_TRY(dupload(s, crp, &rp));
-      AMG_HIP(hipStreamSynchronize(s));
-      *d_crp = rp;
-      *d_ccj = c_col;
-      *d_cv = c_val;
-      *nnz = used;
-      c_col = nullptr;
-      c_val = nullptr;
-      return AMG_OK;
-   };
-   const int st = run();
-   hipFree(c_col);
-   hipFree(c_val);
-   cleanup();
-   return st;
-}
-
-template <class T>
-int download(hipStream_t s, const T *d, size_t n, std::vector<T> &h)
-{
-   h.resize(n);
-   if (n) AMG_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-   return AMG_OK;
-}
-
 } // namespace
 
-// spgemm_dev for the device-resident setup loop (amg_setup_dev.hip)
-int amg_spgemm_dev(hipStream_t s, int An, const int *d_arp, const int *d_acj, const double *d_av, const int *d_brp,
-                   const int *d_bcj, const double *d_bv, int Bm, int **d_crp, int **d_ccj, double **d_cv,
-                   long long *nnz)
+// C = A B with every operand on the device; C's arrays are allocated here
+int spgemm_dev(hipStream_t s, const DCsr &A, const DCsr &B, DCsr &C)
 {
-   return spgemm_dev(s, An, d_arp, d_acj, d_av, d_brp, d_bcj, d_bv, Bm, d_crp, d_ccj, d_cv, nnz);
+   const int An = A.n;
+   DBuf<long long> d_ub, d_hoff, d_ooff;
+   DBuf<int> d_hcol, d_cnt, d_ocol, c_col;
+   DBuf<double> d_hval, d_oval, c_val;
+   long long c_cap = 0;
+   AMG_TRY(d_ub.alloc((size_t)An));
+   if (An > 0) spgemm_ub_k<<<(An + 255) / 256, 256, 0, s>>>(A.rp, A.cj, B.rp, An, d_ub);
+   std::vector<long long> ub;
+   AMG_TRY(download(s, d_ub.p, (size_t)An, ub));
+   AMG_HIP(hipStreamSynchronize(s));
+   // table capacity per row: a power of two >= 2 ub (>= 2)
+   std::vector<long long> capr(An);
+   for (int r = 0; r < An; r++) {
+      long long c = 2;
+      while (c < 2 * ub[r]) c <<= 1;
+      capr[r] = c;
+   }
+   // batches of rows within the scratch budget (12 bytes per slot: 6 GiB by default)
+   const std::vector<int> cut = batch_bounds(capr, g_budget.load());
+   long long maxb = 1;
+   for (size_t b = 0; b + 1 < cut.size(); b++)
+      maxb = std::max(maxb, std::accumulate(capr.begin() + cut[b], capr.begin() + cut[b + 1], 0LL));
+   AMG_TRY(d_hcol.alloc((size_t)maxb));
+   AMG_TRY(d_hval.alloc((size_t)maxb));
+   AMG_TRY(d_hoff.alloc((size_t)An + 1));
+   AMG_TRY(d_ooff.alloc((size_t)An + 1));
+   AMG_TRY(d_cnt.alloc((size_t)An));
+   AMG_TRY(d_ocol.alloc((size_t)maxb));
+   AMG_TRY(d_oval.alloc((size_t)maxb));
+   std::vector<int> crp(An + 1, 0);
+   long long used = 0;
+   for (size_t b = 0; b + 1 < cut.size(); b++) {
+      const int r0 = cut[b], nr = cut[b + 1] - r0;
+      std::vector<long long> hoff(nr + 1, 0);
+      for (int q = 0; q < nr; q++) hoff[q + 1] = hoff[q] + capr[r0 + q];
+      AMG_HIP(hipMemcpyAsync(d_hoff, hoff.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+      spgemm_row_k<<<(nr + 127) / 128, 128, 0, s>>>(A.rp, A.cj, A.v, B.rp, B.cj, B.v, r0, nr, d_hoff, d_hcol, d_hval,
+                                                    d_cnt, A.n == B.m ? 1 : 0);
+      AMG_HIP(hipGetLastError());
+      std::vector<int> cnt;
+      AMG_TRY(download(s, d_cnt.p, (size_t)nr, cnt));
+      AMG_HIP(hipStreamSynchronize(s));
+      std::vector<long long> ooff(nr + 1, 0);
+      for (int q = 0; q < nr; q++) ooff[q + 1] = ooff[q] + cnt[q];
+      AMG_HIP(hipMemcpyAsync(d_ooff, ooff.data(), (nr + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+      spgemm_pack_k<<<nr, 64, 0, s>>>(d_hoff, d_hcol, d_hval, d_ooff, nr, d_ocol, d_oval);
+      // append the batch to C (grown by doubling, device to device)
+      if (used + ooff[nr] > c_cap) {
+         const long long cap = std::max(used + ooff[nr], 2 * c_cap);
+         DBuf<int> nc;
+         DBuf<double> nv;
+         AMG_TRY(nc.alloc((size_t)cap));
+         if (nv.alloc((size_t)cap) != AMG_OK) return amg_set_error(AMG_ERR_OOM, "spgemm_dev: %lld entries", cap);
+         if (used) {
+            AMG_HIP(hipMemcpyAsync(nc, c_col, used * sizeof(int), hipMemcpyDeviceToDevice, s));
+            AMG_HIP(hipMemcpyAsync(nv, c_val, used * sizeof(double), hipMemcpyDeviceToDevice, s));
+         }
+         AMG_HIP(hipStreamSynchronize(s));
+         c_col = std::move(nc);
+         c_val = std::move(nv);
+         c_cap = cap;
+      }
+      if (ooff[nr]) {
+         AMG_HIP(hipMemcpyAsync(c_col.p + used, d_ocol, ooff[nr] * sizeof(int), hipMemcpyDeviceToDevice, s));
+         AMG_HIP(hipMemcpyAsync(c_val.p + used, d_oval, ooff[nr] * sizeof(double), hipMemcpyDeviceToDevice, s));
+      }
+      AMG_HIP(hipStreamSynchronize(s));
+      AMG_TRY(scan_counts(cnt.data(), nr, &crp[r0]));
+      used += ooff[nr];
+   }
+   if (!c_col.p) {
+      AMG_TRY(c_col.alloc(0));
+      AMG_TRY(c_val.alloc(0));
+   }
+   AMG_TRY(upload(s, crp.data(), crp.size(), C.rp));
+   AMG_HIP(hipStreamSynchronize(s)); // crp leaves scope
+   C.n = A.n, C.m = B.m, C.nnz = used;
+   C.cj = std::move(c_col);
+   C.v = std::move(c_val);
+   return AMG_OK;
 }
 
 extern "C" int amg_set_spgemm_scratch(long long slots)
@@ -274,94 +217,41 @@ extern "C" int amg_set_spgemm_scratch(long long slots)
    return AMG_OK;
 }
 
-// C = A B on device `device` (host CSR in and out; bit-identical to the host
-// Gustavson spgemm).  An x Am, B Am x Bm.
-int amg_spgemm_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                      const std::vector<double> &av, int Bn, const std::vector<int> &brp,
-                      const std::vector<int> &bcj, const std::vector<double> &bv, int Bm, std::vector<int> &crp,
-                      std::vector<int> &ccj, std::vector<double> &cv)
+// C = A B on device `device` (bit-identical to the host Gustavson spgemm)
+int amg_spgemm_device(int device, const HCsr &A, const HCsr &B, HCsr &C)
 {
-   (void)Bn;
-   AMG_HIP(hipSetDevice(device));
-   hipStream_t s;
-   AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-   std::vector<void *> mem;
-   int *d_arp = nullptr, *d_acj = nullptr, *d_brp = nullptr, *d_bcj = nullptr, *d_crp = nullptr, *d_ccj = nullptr;
-   double *d_av = nullptr, *d_bv = nullptr, *d_cv = nullptr;
-   long long nnz = 0;
-   auto run = [&]() -> int {
-      AMG_TRY(dupload(s, arp, &d_arp));
-      AMG_TRY(dupload(s, acj, &d_acj));
-      AMG_TRY(dupload(s, av, &d_av));
-      AMG_TRY(dupload(s, brp, &d_brp));
-      AMG_TRY(dupload(s, bcj, &d_bcj));
-      AMG_TRY(dupload(s, bv, &d_bv));
-      AMG_TRY(spgemm_dev(s, An, d_arp, d_acj, d_av, d_brp, d_bcj, d_bv, Bm, &d_crp, &d_ccj, &d_cv, &nnz));
-      AMG_TRY(download(s, d_crp, (size_t)An + 1, crp));
-      AMG_TRY(download(s, d_ccj, (size_t)nnz, ccj));
-      AMG_TRY(download(s, d_cv, (size_t)nnz, cv));
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (void *p : {(void *)d_arp, (void *)d_acj, (void *)d_av, (void *)d_brp, (void *)d_bcj, (void *)d_bv,
-                   (void *)d_crp, (void *)d_ccj, (void *)d_cv})
-      hipFree(p);
-   hipStreamDestroy(s);
-   return st;
+   Session ss;
+   AMG_TRY(ss.open(device));
+   DCsr dA, dB, dC;
+   AMG_TRY(upload_csr(ss.s, view(A), true, dA));
+   AMG_TRY(upload_csr(ss.s, view(B), true, dB));
+   AMG_TRY(spgemm_dev(ss.s, dA, dB, dC));
+   AMG_TRY(download_csr(ss.s, dC, true, C));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
 
 // A_c = R (A P) on device `device`: A, P, R uploaded once, A P kept on the
-// device between the two products, only A_c downloaded (host CSR in and out;
-// bit-identical to the host's two Gustavson products)
-int amg_rap_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                   const std::vector<double> &av, const std::vector<int> &prp, const std::vector<int> &pcj,
-                   const std::vector<double> &pv, int Pm, int Rn, const std::vector<int> &rrp,
-                   const std::vector<int> &rcj, const std::vector<double> &rv, std::vector<int> &crp,
-                   std::vector<int> &ccj, std::vector<double> &cv)
+// device between the two products, only A_c downloaded (bit-identical to the
+// host's two Gustavson products)
+int amg_rap_device(int device, const HCsr &A, const HCsr &P, const HCsr &R, HCsr &Ac)
 {
-   AMG_HIP(hipSetDevice(device));
-   hipStream_t s;
-   AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-   int *d_arp = nullptr, *d_acj = nullptr, *d_prp = nullptr, *d_pcj = nullptr, *d_rrp = nullptr, *d_rcj = nullptr;
-   int *d_aprp = nullptr, *d_apcj = nullptr, *d_crp = nullptr, *d_ccj = nullptr;
-   double *d_av = nullptr, *d_pv = nullptr, *d_rv = nullptr, *d_apv = nullptr, *d_cv = nullptr;
-   long long apnz = 0, cnz = 0;
-   auto run = [&]() -> int {
-      AMG_TRY(dupload(s, arp, &d_arp));
-      AMG_TRY(dupload(s, acj, &d_acj));
-      AMG_TRY(dupload(s, av, &d_av));
-      AMG_TRY(dupload(s, prp, &d_prp));
-      AMG_TRY(dupload(s, pcj, &d_pcj));
-      AMG_TRY(dupload(s, pv, &d_pv));
-      AMG_TRY(spgemm_dev(s, An, d_arp, d_acj, d_av, d_prp, d_pcj, d_pv, Pm, &d_aprp, &d_apcj, &d_apv, &apnz));
-      // A is not needed any more: give its memory back before the second product
-      AMG_HIP(hipStreamSynchronize(s));
-      hipFree(d_acj), d_acj = nullptr;
-      hipFree(d_av), d_av = nullptr;
-      AMG_TRY(dupload(s, rrp, &d_rrp));
-      AMG_TRY(dupload(s, rcj, &d_rcj));
-      AMG_TRY(dupload(s, rv, &d_rv));
-      AMG_TRY(spgemm_dev(s, Rn, d_rrp, d_rcj, d_rv, d_aprp, d_apcj, d_apv, Pm, &d_crp, &d_ccj, &d_cv, &cnz));
-      AMG_TRY(download(s, d_crp, (size_t)Rn + 1, crp));
-      AMG_TRY(download(s, d_ccj, (size_t)cnz, ccj));
-      AMG_TRY(download(s, d_cv, (size_t)cnz, cv));
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (void *p : {(void *)d_arp, (void *)d_acj, (void *)d_av, (void *)d_prp, (void *)d_pcj, (void *)d_pv,
-                   (void *)d_rrp, (void *)d_rcj, (void *)d_rv, (void *)d_aprp, (void *)d_apcj, (void *)d_apv,
-                   (void *)d_crp, (void *)d_ccj, (void *)d_cv})
-      hipFree(p);
-   hipStreamDestroy(s);
-   return st;
+   Session ss;
+   AMG_TRY(ss.open(device));
+   DCsr dA, dP, dR, dAP, dAc;
+   AMG_TRY(upload_csr(ss.s, view(A), true, dA));
+   AMG_TRY(upload_csr(ss.s, view(P), true, dP));
+   AMG_TRY(spgemm_dev(ss.s, dA, dP, dAP));
+   // A is not needed any more: give its memory back before the second product
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   dA.cj.release();
+   dA.v.release();
+   AMG_TRY(upload_csr(ss.s, view(R), true, dR));
+   AMG_TRY(spgemm_dev(ss.s, dR, dAP, dAc));
+   AMG_TRY(download_csr(ss.s, dAc, true, Ac));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
-
-int amg_trunc_dev(hipStream_t s, int n, const int *d_rp, const int *d_cj, const double *d_v, long long nnz, double tf,
-                  int maxel, int **d_orp, int **d_ocj, double **d_ov, long long *onnz); // amg_trunc.hip
 
 namespace {
 
@@ -395,64 +285,32 @@ __global__ __launch_bounds__(256) void smooth_factor_k(const int *__restrict__ a
 // the add_* options off, R~ = P^T GT by spgemm_dev (bit-identical to the host
 // products); with one of them on, P~ is truncated on the device before it is
 // downloaded and R~ is left to the caller (the transpose of the truncated P~).
-// R is P^T (host CSR).
-int amg_smooth_transfer_device(int device, int An, const std::vector<int> &arp, const std::vector<int> &acj,
-                               const std::vector<double> &av, const std::vector<int> &prp,
-                               const std::vector<int> &pcj, const std::vector<double> &pv, int Pm,
-                               const std::vector<int> &rrp, const std::vector<int> &rcj,
-                               const std::vector<double> &rv, double w, int add_max, double add_tf,
-                               std::vector<int> &psrp, std::vector<int> &pscj, std::vector<double> &psv,
-                               std::vector<int> &rsrp, std::vector<int> &rscj, std::vector<double> &rsv)
+// R is P^T.
+int amg_smooth_transfer_device(int device, const HCsr &A, const HCsr &P, const HCsr &R, double w, int add_max,
+                               double add_tf, HCsr &Ps, HCsr &Rs)
 {
-   AMG_HIP(hipSetDevice(device));
-   hipStream_t s;
-   AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-   int *d_arp = nullptr, *d_acj = nullptr, *d_prp = nullptr, *d_pcj = nullptr, *d_rrp = nullptr, *d_rcj = nullptr;
-   int *d_psrp = nullptr, *d_pscj = nullptr, *d_trp = nullptr, *d_tcj = nullptr, *d_rsrp = nullptr, *d_rscj = nullptr;
-   double *d_av = nullptr, *d_g = nullptr, *d_gt = nullptr, *d_pv = nullptr, *d_rv = nullptr, *d_psv = nullptr,
-          *d_tv = nullptr, *d_rsv = nullptr;
-   const bool trunc = add_max > 0 || add_tf > 0.0;
-   auto run = [&]() -> int {
-      AMG_TRY(dupload(s, arp, &d_arp));
-      AMG_TRY(dupload(s, acj, &d_acj));
-      AMG_TRY(dupload(s, av, &d_av));
-      AMG_TRY(dupload(s, prp, &d_prp));
-      AMG_TRY(dupload(s, pcj, &d_pcj));
-      AMG_TRY(dupload(s, pv, &d_pv));
-      AMG_HIP(hipMalloc(&d_g, std::max<size_t>(av.size(), 1) * sizeof(double)));
-      AMG_HIP(hipMalloc(&d_gt, std::max<size_t>(av.size(), 1) * sizeof(double)));
-      smooth_factor_k<<<std::min((An + 3) / 4, 8192), 256, 0, s>>>(d_arp, d_acj, d_av, An, w, d_g, d_gt);
-      AMG_HIP(hipGetLastError());
-      long long psnz = 0, rsnz = 0;
-      AMG_TRY(spgemm_dev(s, An, d_arp, d_acj, d_g, d_prp, d_pcj, d_pv, Pm, &d_psrp, &d_pscj, &d_psv, &psnz));
-      if (trunc) {
-         long long tnz = 0;
-         AMG_TRY(amg_trunc_dev(s, An, d_psrp, d_pscj, d_psv, psnz, add_tf, add_max, &d_trp, &d_tcj, &d_tv, &tnz));
-         AMG_TRY(download(s, d_trp, (size_t)An + 1, psrp));
-         AMG_TRY(download(s, d_tcj, (size_t)tnz, pscj));
-         AMG_TRY(download(s, d_tv, (size_t)tnz, psv));
-      } else {
-         AMG_TRY(download(s, d_psrp, (size_t)An + 1, psrp));
-         AMG_TRY(download(s, d_pscj, (size_t)psnz, pscj));
-         AMG_TRY(download(s, d_psv, (size_t)psnz, psv));
-         AMG_TRY(dupload(s, rrp, &d_rrp));
-         AMG_TRY(dupload(s, rcj, &d_rcj));
-         AMG_TRY(dupload(s, rv, &d_rv));
-         AMG_TRY(spgemm_dev(s, Pm, d_rrp, d_rcj, d_rv, d_arp, d_acj, d_gt, An, &d_rsrp, &d_rscj, &d_rsv, &rsnz));
-         AMG_TRY(download(s, d_rsrp, (size_t)Pm + 1, rsrp));
-         AMG_TRY(download(s, d_rscj, (size_t)rsnz, rscj));
-         AMG_TRY(download(s, d_rsv, (size_t)rsnz, rsv));
-      }
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (void *p : {(void *)d_arp, (void *)d_acj, (void *)d_prp, (void *)d_pcj, (void *)d_rrp, (void *)d_rcj,
-                   (void *)d_psrp, (void *)d_pscj, (void *)d_trp, (void *)d_tcj, (void *)d_rsrp, (void *)d_rscj,
-                   (void *)d_av, (void *)d_g, (void *)d_gt, (void *)d_pv, (void *)d_rv, (void *)d_psv, (void *)d_tv,
-                   (void *)d_rsv})
-      hipFree(p);
-   hipStreamDestroy(s);
-   return st;
+   Session ss;
+   AMG_TRY(ss.open(device));
+   DCsr G, dP, dR, dPs, dT, dRs; // G: A, then A's pattern with the values g, then gt
+   DBuf<double> d_g, d_gt;
+   AMG_TRY(upload_csr(ss.s, view(A), true, G));
+   AMG_TRY(upload_csr(ss.s, view(P), true, dP));
+   AMG_TRY(d_g.alloc((size_t)G.nnz));
+   AMG_TRY(d_gt.alloc((size_t)G.nnz));
+   smooth_factor_k<<<std::min((A.n + 3) / 4, 8192), 256, 0, ss.s>>>(G.rp, G.cj, G.v, A.n, w, d_g, d_gt);
+   AMG_HIP(hipGetLastError());
+   std::swap(G.v, d_g);
+   AMG_TRY(spgemm_dev(ss.s, G, dP, dPs));
+   if (add_max > 0 || add_tf > 0.0) {
+      AMG_TRY(trunc_dev(ss.s, dPs, add_tf, add_max, dT));
+      AMG_TRY(download_csr(ss.s, dT, true, Ps));
+   } else {
+      AMG_TRY(download_csr(ss.s, dPs, true, Ps));
+      AMG_TRY(upload_csr(ss.s, view(R), true, dR));
+      std::swap(G.v, d_gt);
+      AMG_TRY(spgemm_dev(ss.s, dR, G, dRs));
+      AMG_TRY(download_csr(ss.s, dRs, true, Rs));
+   }
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }

@@ -17,13 +17,13 @@
 // The serial sums are formed by every lane alike from wave-uniform broadcasts
 // of the chunk's values in storage order, so they are the host's sums.  The
 // row kernel leaves one keep flag per entry, the kept count and (f1, f2) per
-// row; the counts are scanned on the host (spgemm_dev's scheme: the entry
-// count sizes the output) and the pack kernel writes kept entries in column
+// row; the counts are scanned on the host (amg_csr.h's rowptr_of_counts: the
+// entry count sizes the output) and the pack kernel writes kept entries in column
 // order with their value rescaled by one multiply per pass that dropped.
 #include <algorithm>
 #include <vector>
 
-#include "amg_internal.h"
+#include "amg_csr.h"
 
 namespace {
 
@@ -154,85 +154,41 @@ __global__ __launch_bounds__(TRUNC_BLOCK) void trunc_pack_k(const int *__restric
 
 } // namespace
 
-// rows of a device CSR truncated (trunc_factor, max_elmts): the result's rowptr /
-// col / val are allocated here and its entry count returned in *onnz
-int amg_trunc_dev(hipStream_t s, int n, const int *d_rp, const int *d_cj, const double *d_v, long long nnz, double tf,
-                  int maxel, int **d_orp, int **d_ocj, double **d_ov, long long *onnz)
+// rows of a device CSR truncated (trunc_factor, max_elmts); T's arrays are allocated here
+int trunc_dev(hipStream_t s, const DCsr &M, double tf, int maxel, DCsr &T)
 {
-   unsigned char *d_keep = nullptr;
-   int *d_cnt = nullptr, *d_mode = nullptr, *orp = nullptr, *ocj = nullptr;
-   double *d_fac = nullptr, *ov = nullptr;
-   auto run = [&]() -> int {
-      AMG_HIP(hipMalloc(&d_keep, (size_t)std::max(nnz, 1LL)));
-      AMG_HIP(hipMalloc(&d_cnt, (size_t)n * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_mode, (size_t)n * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_fac, 2 * (size_t)n * sizeof(double)));
-      const int wpb = TRUNC_BLOCK / 64;
-      const int grid = (int)std::min<long long>(((long long)n + wpb - 1) / wpb, 8192);
-      trunc_row_k<<<grid, TRUNC_BLOCK, 0, s>>>(d_rp, d_cj, d_v, n, tf, maxel, d_keep, d_cnt, d_fac, d_mode);
-      AMG_HIP(hipGetLastError());
-      std::vector<int> cnt(n), rp(n + 1, 0);
-      AMG_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-      AMG_HIP(hipStreamSynchronize(s));
-      for (int r = 0; r < n; r++) rp[r + 1] = rp[r] + cnt[r];
-      AMG_HIP(hipMalloc(&orp, ((size_t)n + 1) * sizeof(int)));
-      AMG_HIP(hipMalloc(&ocj, (size_t)std::max(rp[n], 1) * sizeof(int)));
-      AMG_HIP(hipMalloc(&ov, (size_t)std::max(rp[n], 1) * sizeof(double)));
-      AMG_HIP(hipMemcpyAsync(orp, rp.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-      trunc_pack_k<<<grid, TRUNC_BLOCK, 0, s>>>(d_rp, d_cj, d_v, n, d_keep, orp, d_fac, d_mode, ocj, ov);
-      AMG_HIP(hipGetLastError());
-      AMG_HIP(hipStreamSynchronize(s)); // rp leaves scope
-      *onnz = rp[n];
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (void *p : {(void *)d_keep, (void *)d_cnt, (void *)d_mode, (void *)d_fac}) hipFree(p);
-   if (st != AMG_OK) {
-      for (void *p : {(void *)orp, (void *)ocj, (void *)ov}) hipFree(p);
-      return st;
-   }
-   *d_orp = orp;
-   *d_ocj = ocj;
-   *d_ov = ov;
+   const int n = M.n;
+   DBuf<unsigned char> d_keep;
+   DBuf<int> d_cnt, d_mode;
+   DBuf<double> d_fac;
+   AMG_TRY(d_keep.alloc((size_t)M.nnz));
+   AMG_TRY(d_cnt.alloc((size_t)n));
+   AMG_TRY(d_mode.alloc((size_t)n));
+   AMG_TRY(d_fac.alloc(2 * (size_t)n));
+   const int wpb = TRUNC_BLOCK / 64;
+   const int grid = (int)std::min<long long>(((long long)n + wpb - 1) / wpb, 8192);
+   trunc_row_k<<<grid, TRUNC_BLOCK, 0, s>>>(M.rp, M.cj, M.v, n, tf, maxel, d_keep, d_cnt, d_fac, d_mode);
+   AMG_HIP(hipGetLastError());
+   std::vector<int> rp;
+   AMG_TRY(rowptr_of_counts(s, d_cnt, n, rp, T.rp));
+   T.n = M.n, T.m = M.m, T.nnz = rp[n];
+   AMG_TRY(T.cj.alloc((size_t)T.nnz));
+   AMG_TRY(T.v.alloc((size_t)T.nnz));
+   trunc_pack_k<<<grid, TRUNC_BLOCK, 0, s>>>(M.rp, M.cj, M.v, n, d_keep, T.rp, d_fac, d_mode, T.cj, T.v);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipStreamSynchronize(s)); // rp leaves scope
    return AMG_OK;
 }
 
 // host CSR in and out through device `device` (bit-identical to truncate_rows)
-int amg_truncate_device(int device, int n, const int *rp, const int *cj, const double *v, double tf, int maxel,
-                        std::vector<int> &orp, std::vector<int> &ocj, std::vector<double> &ov)
+int amg_truncate_device(int device, const HCsrView &M, double tf, int maxel, HCsr &T)
 {
-   AMG_HIP(hipSetDevice(device));
-   hipStream_t s;
-   AMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-   const long long nnz = rp[n];
-   int *d_rp = nullptr, *d_cj = nullptr, *d_orp = nullptr, *d_ocj = nullptr;
-   double *d_v = nullptr, *d_ov = nullptr;
-   long long onnz = 0;
-   auto run = [&]() -> int {
-      AMG_HIP(hipMalloc(&d_rp, ((size_t)n + 1) * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_cj, (size_t)std::max(nnz, 1LL) * sizeof(int)));
-      AMG_HIP(hipMalloc(&d_v, (size_t)std::max(nnz, 1LL) * sizeof(double)));
-      AMG_HIP(hipMemcpyAsync(d_rp, rp, ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-      if (nnz) {
-         AMG_HIP(hipMemcpyAsync(d_cj, cj, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
-         AMG_HIP(hipMemcpyAsync(d_v, v, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, s));
-      }
-      AMG_TRY(amg_trunc_dev(s, n, d_rp, d_cj, d_v, nnz, tf, maxel, &d_orp, &d_ocj, &d_ov, &onnz));
-      orp.resize((size_t)n + 1);
-      ocj.resize((size_t)onnz);
-      ov.resize((size_t)onnz);
-      AMG_HIP(hipMemcpyAsync(orp.data(), d_orp, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-      if (onnz) {
-         AMG_HIP(hipMemcpyAsync(ocj.data(), d_ocj, (size_t)onnz * sizeof(int), hipMemcpyDeviceToHost, s));
-         AMG_HIP(hipMemcpyAsync(ov.data(), d_ov, (size_t)onnz * sizeof(double), hipMemcpyDeviceToHost, s));
-      }
-      AMG_HIP(hipStreamSynchronize(s));
-      return AMG_OK;
-   };
-   const int st = run();
-   hipStreamSynchronize(s);
-   for (void *p : {(void *)d_rp, (void *)d_cj, (void *)d_v, (void *)d_orp, (void *)d_ocj, (void *)d_ov}) hipFree(p);
-   hipStreamDestroy(s);
-   return st;
+   Session ss;
+   AMG_TRY(ss.open(device));
+   DCsr dM, dT;
+   AMG_TRY(upload_csr(ss.s, M, true, dM));
+   AMG_TRY(trunc_dev(ss.s, dM, tf, maxel, dT));
+   AMG_TRY(download_csr(ss.s, dT, true, T));
+   AMG_HIP(hipStreamSynchronize(ss.s));
+   return AMG_OK;
 }
