@@ -25,6 +25,40 @@
 namespace amgk {
 
 // ---------------------------------------------------------------------------
+// Host launch helpers: runtime value -> template argument.  f is a generic
+// lambda that takes the value as a std::integral_constant / bool_constant (read
+// it as `decltype(v)::value`); the legal values stand at the call:
+//    pick_int<2, 4, 8>(ru, otherwise<6>, f)   ru in {2, 4, 8}, any other value: 6
+// Every listed value instantiates f, so where only some combinations of two
+// arguments exist as kernels the calls nest (or f uses `if constexpr`), never
+// a cross product.
+// ---------------------------------------------------------------------------
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int V>
+constexpr int_c<V> otherwise{};
+
+template <class F>
+static inline void pick_bool(bool b, F &&f)
+{
+   if (b) f(std::true_type{});
+   else f(std::false_type{});
+}
+
+template <int... Vs, int D, class F>
+static inline void pick_int(int v, int_c<D>, F &&f)
+{
+   if (!((v == Vs && (f(int_c<Vs>{}), true)) || ...)) f(int_c<D>{});
+}
+
+// a process-wide integer tuning knob: `dflt` when the variable is unset
+static inline int env_int(const char *name, int dflt)
+{
+   const char *v = std::getenv(name);
+   return v ? std::atoi(v) : dflt;
+}
+
+// ---------------------------------------------------------------------------
 // deterministic workgroup reduction of one double per lane (256 lanes)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double block_sum_256(double v, double *lds4)
@@ -711,6 +745,27 @@ struct MpSten {
    double val[AMG_MP_MAXJ];
 };
 
+// the master list as a kernel argument: offsets and the uniform values
+static MpSten mp_sten(const amg_mat *A)
+{
+   MpSten S;
+   for (int j = 0; j < AMG_MP_MAXJ; j++) {
+      S.off[j] = A->mp_off[j];
+      S.val[j] = A->mp_val[j];
+   }
+   return S;
+}
+
+// the 27-pt march's: without uniform values its 27 entries carry the dominant
+// pattern's (mz_domval, not mp_val)
+static MpSten mp_sten27(const amg_mat *A)
+{
+   MpSten S = mp_sten(A);
+   if (!A->mp_uni)
+      for (int j = 0; j < 27; j++) S.val[j] = A->mz_domval[j];
+   return S;
+}
+
 // exact per-entry gather (csr_mp_kernel FORM 1): row 2t's operand loaded only
 // when it uses the entry, row 2t+1's likewise, one 16-byte load when both do
 template <int NEG, int JM, bool UNI>
@@ -912,29 +967,18 @@ template <int NEG, bool NEED_DIAG, class Epi>
 static void launch_mp(hipStream_t s, const amg_mat *A, const double *x, int rb, int re, const Epi &e,
                       double *partials)
 {
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_val[j];
-   }
+   const MpSten S = mp_sten(A);
    const int nb = (re - rb + 1023) / 1024;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
    const size_t lds = A->mp_uni ? 0 : (size_t)A->pp_n * A->mp_J * sizeof(v2d);
-   if (A->mp_J <= 8) {
-      if (A->mp_uni)
-         csr_mp_kernel<NEG, NEED_DIAG, Epi, 8, true><<<nb, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, A->mp_J,
-                                                                      S, x, A->ncols, rb, re, e, partials);
-      else
-         csr_mp_kernel<NEG, NEED_DIAG, Epi, 8, false><<<nb, 256, lds, s>>>(A->ppat, A->mpmask, A->pp_n, mv,
-                                                                         A->mp_J, S, x, A->ncols, rb, re, e, partials);
-   } else {
-      if (A->mp_uni)
-         csr_mp_kernel<NEG, NEED_DIAG, Epi, AMG_MP_MAXJ, true><<<nb, 256, 0, s>>>(
+   // the unrolled master walk covers 8 entries or the whole list
+   pick_bool(A->mp_J <= 8, [&](auto j8) {
+      constexpr int JM = decltype(j8)::value ? 8 : AMG_MP_MAXJ;
+      pick_bool(A->mp_uni, [&](auto uni) {
+         csr_mp_kernel<NEG, NEED_DIAG, Epi, JM, decltype(uni)::value><<<nb, 256, lds, s>>>(
             A->ppat, A->mpmask, A->pp_n, mv, A->mp_J, S, x, A->ncols, rb, re, e, partials);
-      else
-         csr_mp_kernel<NEG, NEED_DIAG, Epi, AMG_MP_MAXJ, false><<<nb, 256, lds, s>>>(
-            A->ppat, A->mpmask, A->pp_n, mv, A->mp_J, S, x, A->ncols, rb, re, e, partials);
-   }
+      });
+   });
 }
 
 // ---------------------------------------------------------------------------
@@ -1226,106 +1270,76 @@ static int occ_chunk(const amg_mat *A, int nk, int npb, int occ, const void *fn)
 
 struct EpiGemv; // below
 
+// AMG_MZ_WPE=8: registers capped for 8 waves per SIMD (one line, prefetch 1);
+// =5: the halo-prefetch form held to 5 waves per SIMD
+static int knob_mz_wpe()
+{
+   static const int v = env_int("AMG_MZ_WPE", 0);
+   return v;
+}
+// AMG_MZ_HPF: 1 / 2 the halo operands one / two planes ahead, 3 / 4 with the
+// right-hand side too (default, and any other value, 3: 90 VGPRs, 5 waves per
+// SIMD; profiles/r05/hpf/)
+static int knob_mz_hpf()
+{
+   static const int v = env_int("AMG_MZ_HPF", 3);
+   return v;
+}
+// AMG_MZ_LDSPAD: dynamic LDS bytes per workgroup that cap the resident
+// workgroups per CU (an occupancy experiment; the kernel does not use them)
+static int knob_mz_ldspad()
+{
+   static const int v = env_int("AMG_MZ_LDSPAD", 0);
+   return v;
+}
+
 template <int NEG, bool NEED_DIAG, class Epi>
 static void launch_mz(hipStream_t s, const amg_mat *A, const double *x, const Epi &e, double *partials, int kb,
                       int ke)
 {
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_val[j];
-   }
+   const MpSten S = mp_sten(A);
    const int P = A->mz_P, nz = A->nrows / P, Sx = A->mz_S, nk = ke - kb;
    if (nk <= 0) return;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
    // two or four lines per lane (ctx->mz_lines; SpMV / SpGEMV: ctx->mz_lines_gemv)
    // where the plane splits into line groups; ctx->mz_pf: prefetch distance
    const int lines = std::is_same<Epi, EpiGemv>::value ? A->ctx->mz_lines_gemv : A->ctx->mz_lines;
-   const bool pf2 = A->ctx->mz_pf == 2;
-   // AMG_MZ_WPE=8: registers capped for 8 waves per SIMD (one line, prefetch 1)
-   static const int wpe = [] {
-      const char *v = std::getenv("AMG_MZ_WPE");
-      return v ? std::atoi(v) : 0;
-   }();
+   const int wpe = knob_mz_wpe();
    // ctx->mz_pf == 3: prefetch 1 with the halo operands two planes ahead (HPF, one line per lane)
-   const int pfk = A->ctx->mz_pf == 3 && lines == 1 ? 3 : (pf2 ? 2 : 1);
+   const bool hpf = A->ctx->mz_pf == 3 && lines == 1;
    auto go = [&](auto uni, auto nln, auto pf) {
       constexpr bool U = decltype(uni)::value;
       constexpr int N = decltype(nln)::value, F = decltype(pf)::value;
+      // the instantiation that is launched also sizes its own chunk (occ_chunk)
+      auto run = [&](auto wv, auto dv, size_t lds) {
+         constexpr int W = decltype(wv)::value, D = decltype(dv)::value;
+         const void *fn = (const void *)csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, W, D>;
+         const int npb = P / (512 * N), zc = occ_chunk(A, nk, npb, A->ctx->mz_occ, fn), nch = (nk + zc - 1) / zc;
+         csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, W, D><<<npb * nch, 256, lds, s>>>(
+            A->ppat, A->mpmask, A->pp_n, mv, S, x, P, Sx, nz, zc, npb, A->ctx->mz_xcd, e, partials, kb, ke);
+      };
+      // the register-capped and halo-prefetch forms exist for one line, prefetch 1 only
       if constexpr (N == 1 && F == 1) {
-         if (pfk == 3) {
-            auto hpf = [&](auto wv, auto dv) {
-               constexpr int W = decltype(wv)::value, D = decltype(dv)::value;
-               const void *fnh = (const void *)csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, W, D>;
-               const int npb = P / 512, zc = occ_chunk(A, nk, npb, A->ctx->mz_occ, fnh), nch = (nk + zc - 1) / zc;
-               csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, W, D><<<npb * nch, 256, 0, s>>>(
-                  A->ppat, A->mpmask, A->pp_n, mv, S, x, P, Sx, nz, zc, npb, A->ctx->mz_xcd, e, partials, kb, ke);
-            };
-            using W0 = std::integral_constant<int, 0>;
-            using W5 = std::integral_constant<int, 5>;
-            // AMG_MZ_HPF: 1 / 2 the halo operands one / two planes ahead, 3 / 4
-            // with the right-hand side too (default 3: 90 VGPRs, 5 waves per
-            // SIMD; profiles/r05/hpf/); AMG_MZ_WPE=5: held to 5 waves per SIMD
-            static const int hd = [] {
-               const char *v = std::getenv("AMG_MZ_HPF");
-               const int d = v ? std::atoi(v) : 3;
-               return d >= 1 && d <= 4 ? d : 3;
-            }();
-            switch (hd * 2 + (wpe == 5)) {
-            case 2: hpf(W0{}, std::integral_constant<int, 1>{}); break;
-            case 3: hpf(W5{}, std::integral_constant<int, 1>{}); break;
-            case 5: hpf(W5{}, std::integral_constant<int, 2>{}); break;
-            case 6: hpf(W0{}, std::integral_constant<int, 3>{}); break;
-            case 7: hpf(W5{}, std::integral_constant<int, 3>{}); break;
-            case 8: hpf(W0{}, std::integral_constant<int, 4>{}); break;
-            case 9: hpf(W5{}, std::integral_constant<int, 4>{}); break;
-            default: hpf(W0{}, std::integral_constant<int, 2>{}); break;
-            }
+         if (hpf) {
+            pick_int<1, 2, 4>(knob_mz_hpf(), otherwise<3>, [&](auto d) {
+               pick_int<5>(wpe, otherwise<0>, [&](auto w) { run(w, d, 0); });
+            });
             return;
          }
-      }
-      if constexpr (N == 1 && F == 1) {
          if (wpe == 8) {
-            const void *fn8 = (const void *)csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, 8>;
-            const int npb = P / 512, zc = occ_chunk(A, nk, npb, A->ctx->mz_occ, fn8), nch = (nk + zc - 1) / zc;
-            csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F, 8><<<npb * nch, 256, 0, s>>>(
-               A->ppat, A->mpmask, A->pp_n, mv, S, x, P, Sx, nz, zc, npb, A->ctx->mz_xcd, e, partials, kb, ke);
+            run(int_c<8>{}, int_c<0>{}, 0);
             return;
          }
       }
-      const void *fn = (const void *)csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F>;
-      const int npb = P / (512 * N), zc = occ_chunk(A, nk, npb, A->ctx->mz_occ, fn), nch = (nk + zc - 1) / zc;
-      // AMG_MZ_LDSPAD: dynamic LDS bytes per workgroup that cap the resident
-      // workgroups per CU (an occupancy experiment; the kernel does not use them)
-      static const int ldspad = [] {
-         const char *v = std::getenv("AMG_MZ_LDSPAD");
-         return v ? std::atoi(v) : 0;
-      }();
-      csr_mz_kernel<NEG, NEED_DIAG, Epi, U, N, F><<<npb * nch, 256, (size_t)ldspad, s>>>(
-         A->ppat, A->mpmask, A->pp_n, mv, S, x, P, Sx, nz, zc, npb, A->ctx->mz_xcd, e, partials, kb, ke);
+      run(int_c<0>{}, int_c<0>{}, (size_t)knob_mz_ldspad());
    };
-   using T = std::true_type;
-   using F = std::false_type;
-   using I1 = std::integral_constant<int, 1>;
-   using I2 = std::integral_constant<int, 2>;
-   using I4 = std::integral_constant<int, 4>;
-   if (A->mp_uni && lines > 1 && Sx % 512 == 0 && (P / Sx) % lines == 0) {
-      if (lines == 4) {
-         if (pf2) go(T{}, I4{}, I2{});
-         else go(T{}, I4{}, I1{});
-      } else {
-         if (pf2) go(T{}, I2{}, I2{});
-         else go(T{}, I2{}, I1{});
-      }
-      return;
-   }
-   if (A->mp_uni) {
-      if (pf2) go(T{}, I1{}, I2{});
-      else go(T{}, I1{}, I1{});
-   } else {
-      if (pf2) go(F{}, I1{}, I2{});
-      else go(F{}, I1{}, I1{});
-   }
+   pick_int<2>(A->ctx->mz_pf, otherwise<1>, [&](auto pf) {
+      // several lines per lane: uniform values only
+      if (A->mp_uni && lines > 1 && Sx % 512 == 0 && (P / Sx) % lines == 0)
+         pick_int<4>(lines, otherwise<2>, [&](auto nln) { go(std::true_type{}, nln, pf); });
+      else
+         pick_bool(A->mp_uni, [&](auto uni) { go(uni, int_c<1>{}, pf); });
+   });
 }
 
 // ---------------------------------------------------------------------------
@@ -1695,67 +1709,45 @@ template <int NEG, bool NEED_DIAG, class Epi>
 static void launch_mz27(hipStream_t s, const amg_mat *A, const double *x, const Epi &e, double *partials, int kb,
                         int ke)
 {
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_uni ? A->mp_val[j] : A->mz_domval[j];
-   }
+   const MpSten S = mp_sten27(A);
    const int P = A->mz_P, nz = A->nrows / P, nk = ke - kb;
    if (nk <= 0) return;
    const int npb = P / 512;
-   // whole rounds of resident workgroups (mz27_occ per CU, the VGPR-limited
-   // occupancy of this kernel)
-   const void *fn;
-   if (A->ctx->mz27_pf == 2)
-      fn = A->mp_uni ? (const void *)csr_mz27_kernel<NEG, NEED_DIAG, Epi, true, 2>
-                     : (const void *)csr_mz27_kernel<NEG, NEED_DIAG, Epi, false, 2>;
-   else
-      fn = A->mp_uni ? (const void *)csr_mz27_kernel<NEG, NEED_DIAG, Epi, true, 1>
-                     : (const void *)csr_mz27_kernel<NEG, NEED_DIAG, Epi, false, 1>;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
    Val27 H;
    for (int j = 0; j < 27; j++) H.v[j] = A->mz_hival[j];
-   // the x-edge fast path needs the dominant pattern (ctx->mz_edge: on)
-   const int xlo = A->ctx->mz_edge ? A->mz_xlo : -1, xhi = A->ctx->mz_edge ? A->mz_xhi : -1;
-   if (A->ctx->mz27_pf == 3 && A->mz_S <= 512) {
-      // the LDS plane-ring form: four workgroups per CU at S = 256 (33 KB ring)
-      const size_t lds = (size_t)4 * (258 + A->mz_S) * sizeof(v2d);
-      const void *fl = A->mp_uni ? (const void *)csr_mz27l_kernel<NEG, NEED_DIAG, Epi, true>
-                                 : (const void *)csr_mz27l_kernel<NEG, NEED_DIAG, Epi, false>;
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fl, 256, lds) != hipSuccess) {
-         (void)hipGetLastError();
-         occ = 0;
+   // the dominant pattern and its x-edge fast path (ctx->mz_edge: on); uniform
+   // values need neither
+   const bool edge = !A->mp_uni && A->ctx->mz_edge && A->mz_dom >= 0;
+   const int dom = A->mp_uni ? -1 : A->mz_dom, xlo = edge ? A->mz_xlo : -1, xhi = edge ? A->mz_xhi : -1;
+   pick_bool(A->mp_uni, [&](auto uni) {
+      constexpr bool U = decltype(uni)::value;
+      if (A->ctx->mz27_pf == 3 && A->mz_S <= 512) {
+         // the LDS plane-ring form: four workgroups per CU at S = 256 (33 KB ring)
+         const size_t lds = (size_t)4 * (258 + A->mz_S) * sizeof(v2d);
+         int occ = 0;
+         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &occ, (const void *)csr_mz27l_kernel<NEG, NEED_DIAG, Epi, U>, 256, lds) != hipSuccess) {
+            (void)hipGetLastError();
+            occ = 0;
+         }
+         const int zc = occ_chunk(A, nk, npb, occ > 0 ? occ : 0, nullptr), nch = (nk + zc - 1) / zc;
+         csr_mz27l_kernel<NEG, NEED_DIAG, Epi, U><<<npb * nch, 256, lds, s>>>(
+            A->ppat, A->mpmask, A->pp_n, mv, S, dom, xlo, xhi, H, x, P, A->mz_S, nz, zc, npb, A->ctx->mz_xcd, e,
+            partials, kb, ke);
+         return;
       }
-      const int zcl = occ_chunk(A, nk, npb, occ > 0 ? occ : 0, nullptr);
-      const int nchl = (nk + zcl - 1) / zcl;
-      if (A->mp_uni)
-         csr_mz27l_kernel<NEG, NEED_DIAG, Epi, true><<<npb * nchl, 256, lds, s>>>(
-            A->ppat, A->mpmask, A->pp_n, mv, S, -1, -1, -1, H, x, P, A->mz_S, nz, zcl, npb, A->ctx->mz_xcd, e,
+      pick_int<2>(A->ctx->mz27_pf, otherwise<1>, [&](auto pf) {
+         constexpr int PF = decltype(pf)::value;
+         // whole rounds of resident workgroups (mz27_occ per CU, or the launched
+         // kernel's VGPR-limited occupancy)
+         const void *fn = (const void *)csr_mz27_kernel<NEG, NEED_DIAG, Epi, U, PF>;
+         const int zc = occ_chunk(A, nk, npb, A->ctx->mz27_occ, fn), nch = (nk + zc - 1) / zc;
+         csr_mz27_kernel<NEG, NEED_DIAG, Epi, U, PF><<<npb * nch, 256, 0, s>>>(
+            A->ppat, A->mpmask, A->pp_n, mv, S, dom, xlo, xhi, H, x, P, A->mz_S, nz, zc, npb, A->ctx->mz_xcd, e,
             partials, kb, ke);
-      else
-         csr_mz27l_kernel<NEG, NEED_DIAG, Epi, false><<<npb * nchl, 256, lds, s>>>(
-            A->ppat, A->mpmask, A->pp_n, mv, S, A->mz_dom, A->mz_dom >= 0 ? xlo : -1, A->mz_dom >= 0 ? xhi : -1,
-            H, x, P, A->mz_S, nz, zcl, npb, A->ctx->mz_xcd, e, partials, kb, ke);
-      return;
-   }
-   const int zc = occ_chunk(A, nk, npb, A->ctx->mz27_occ, fn);
-   const int nch = (nk + zc - 1) / zc;
-   auto go = [&](auto pf) {
-      constexpr int PF = decltype(pf)::value;
-      if (A->mp_uni)
-         csr_mz27_kernel<NEG, NEED_DIAG, Epi, true, PF><<<npb * nch, 256, 0, s>>>(
-            A->ppat, A->mpmask, A->pp_n, mv, S, -1, -1, -1, H, x, P, A->mz_S, nz, zc, npb, A->ctx->mz_xcd, e,
-            partials, kb, ke);
-      else
-         csr_mz27_kernel<NEG, NEED_DIAG, Epi, false, PF><<<npb * nch, 256, 0, s>>>(
-            A->ppat, A->mpmask, A->pp_n, mv, S, A->mz_dom, A->mz_dom >= 0 ? xlo : -1, A->mz_dom >= 0 ? xhi : -1,
-            H, x, P, A->mz_S, nz, zc, npb, A->ctx->mz_xcd, e, partials, kb, ke);
-   };
-   if (A->ctx->mz27_pf == 2)
-      go(std::integral_constant<int, 2>{});
-   else
-      go(std::integral_constant<int, 1>{});
+      });
+   });
 }
 
 // ---------------------------------------------------------------------------
@@ -1852,6 +1844,14 @@ void geo_check(hipStream_t s, const amg_mat *M, int mode, const GeoT &g, int *ba
 struct Val7 {
    double v[7];
 };
+
+// the 7-pt master list's uniform values as a kernel argument
+static Val7 val7(const amg_mat *A)
+{
+   Val7 S;
+   for (int j = 0; j < 7; j++) S.v[j] = A->mp_val[j];
+   return S;
+}
 
 // RING: the wave-edge residuals travel through an LDS ring of RR planes
 // between adjacent waves, ordered by per-wave produced / consumed plane
@@ -2219,8 +2219,7 @@ void mz_residual_restrict(hipStream_t s, const amg_mat *A, const double *f, cons
    if (Ke < 0) Ke = g.nz / 2;
    if (Ke <= Kb) return;
    const int nzm = A->nrows / (g.nx * g.ny);
-   Val7 S;
-   for (int j = 0; j < 7; j++) S.v[j] = A->mp_val[j];
+   const Val7 S = val7(A);
    const int lpl = g.nx / 2, groups = 256 / lpl;
    const int LC = ((g.ny / 2) % (2 * groups) == 0 && A->ctx->rr_lines == 2) ? 2 : 1;
    const int nlb = (g.ny / 2) / (groups * LC);
@@ -2229,21 +2228,22 @@ void mz_residual_restrict(hipStream_t s, const amg_mat *A, const double *f, cons
    const int nb = nlb * nch;
    const int xcd = A->ctx->mz_xcd;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
-#define AMG_RR(U, L, ...) \
-   mz_res_restrict_kernel<U, L, ##__VA_ARGS__><<<nb, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, f, wdev, g.nx, g.ny, \
-                                                   g.nz, zcc, nlb, xcd, stream_hint(A), fc, Kb, Ke, fz0, cz0, nzm, zg)
-   if (A->mp_uni) {
-      if (LC == 2) AMG_RR(true, 2);
-      else if (A->ctx->rr_fpf == 3) AMG_RR(true, 1, 1, false, false, true); // 136 VGPRs, 3 waves / SIMD
-      else if (A->ctx->rr_fpf) AMG_RR(true, 1, 4, false, false, true);      // held to 4 waves (128, 5 spilled)
-      else if (A->ctx->rr_occ == 5) AMG_RR(true, 1, 5);
-      else if (A->ctx->rr_ring) AMG_RR(true, 1, 1, true);
-      else AMG_RR(true, 1);
-   } else {
-      if (LC == 2) AMG_RR(false, 2);
-      else AMG_RR(false, 1);
-   }
-#undef AMG_RR
+   auto run = [&](auto uni, auto lc, auto occ, auto ring, auto fpf) {
+      mz_res_restrict_kernel<decltype(uni)::value, decltype(lc)::value, decltype(occ)::value, decltype(ring)::value,
+                             false, decltype(fpf)::value><<<nb, 256, 0, s>>>(
+         A->ppat, A->mpmask, A->pp_n, mv, S, u, f, wdev, g.nx, g.ny, g.nz, zcc, nlb, xcd, stream_hint(A), fc, Kb, Ke,
+         fz0, cz0, nzm, zg);
+   };
+   using T = std::true_type;
+   using F = std::false_type;
+   // only the one-line uniform form has occupancy / ring / prefetch variants
+   if (LC == 2) pick_bool(A->mp_uni, [&](auto uni) { run(uni, int_c<2>{}, int_c<1>{}, F{}, F{}); });
+   else if (!A->mp_uni) run(F{}, int_c<1>{}, int_c<1>{}, F{}, F{});
+   else if (A->ctx->rr_fpf == 3) run(T{}, int_c<1>{}, int_c<1>{}, F{}, T{}); // 136 VGPRs, 3 waves / SIMD
+   else if (A->ctx->rr_fpf) run(T{}, int_c<1>{}, int_c<4>{}, F{}, T{});      // held to 4 waves (128, 5 spilled)
+   else if (A->ctx->rr_occ == 5) run(T{}, int_c<1>{}, int_c<5>{}, F{}, F{});
+   else if (A->ctx->rr_ring) run(T{}, int_c<1>{}, int_c<1>{}, T{}, F{});
+   else run(T{}, int_c<1>{}, int_c<1>{}, F{}, F{});
 }
 
 // rc = R (r + (-w) A (r ./ a)) for a marched uniform 7-pt level with geometric
@@ -2254,22 +2254,18 @@ void mz_xfer_restrict(hipStream_t s, const amg_mat *A, const double *r, const Ge
    if (Ke < 0) Ke = g.nz / 2;
    if (Ke <= Kb) return;
    const int nzm = A->nrows / (g.nx * g.ny);
-   Val7 S;
-   for (int j = 0; j < 7; j++) S.v[j] = A->mp_val[j];
+   const Val7 S = val7(A);
    const int lpl = g.nx / 2, groups = 256 / lpl;
    const int LC = ((g.ny / 2) % (2 * groups) == 0 && A->ctx->rr_lines == 2) ? 2 : 1;
    const int nlb = (g.ny / 2) / (groups * LC);
    const int zcc = rr_chunk(A);
    const int nb = nlb * ((Ke - Kb + zcc - 1) / zcc);
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
-   if (LC == 2)
-      mz_res_restrict_kernel<true, 2, 1, false, true><<<nb, 256, 0, s>>>(
+   pick_int<2>(LC, otherwise<1>, [&](auto lc) {
+      mz_res_restrict_kernel<true, decltype(lc)::value, 1, false, true><<<nb, 256, 0, s>>>(
          A->ppat, A->mpmask, A->pp_n, mv, S, r, nullptr, wdev, g.nx, g.ny, g.nz, zcc, nlb, A->ctx->mz_xcd, 0, rc, Kb,
          Ke, fz0, cz0, nzm, ZeroGuess(), -omega);
-   else
-      mz_res_restrict_kernel<true, 1, 1, false, true><<<nb, 256, 0, s>>>(
-         A->ppat, A->mpmask, A->pp_n, mv, S, r, nullptr, wdev, g.nx, g.ny, g.nz, zcc, nlb, A->ctx->mz_xcd, 0, rc, Kb,
-         Ke, fz0, cz0, nzm, ZeroGuess(), -omega);
+   });
 }
 
 // Geometric prolongation + correction u += P e (SMEM_Sync_SpGEMV(P, e, u, 1, 1,
@@ -2528,12 +2524,10 @@ void geo_prolong(hipStream_t s, const GeoT &g, const double *wdev, const double 
       int zc = zc0;
       while (zc > 2 && (long long)nseg * ((nzl + zc - 1) / zc) < 2048) zc >>= 1;
       const long long G = (long long)nseg * ((nzl + zc - 1) / zc);
-      if (pf == 2)
-         geo_prolong_march_k<2><<<(unsigned)G, 256, 0, s>>>(e, u, wdev, g.nx, g.ny, g.nz, zb, ze, fz0, cz0, zc, nseg,
-                                                            1, assign, pnt);
-      else
-         geo_prolong_march_k<1><<<(unsigned)G, 256, 0, s>>>(e, u, wdev, g.nx, g.ny, g.nz, zb, ze, fz0, cz0, zc, nseg,
-                                                            1, assign, pnt);
+      pick_int<2>(pf, otherwise<1>, [&](auto pfc) {
+         geo_prolong_march_k<decltype(pfc)::value><<<(unsigned)G, 256, 0, s>>>(e, u, wdev, g.nx, g.ny, g.nz, zb, ze,
+                                                                               fz0, cz0, zc, nseg, 1, assign, pnt);
+      });
       return;
    }
    geo_prolong_k<<<(unsigned)((np + 255) / 256), 256, 0, s>>>(e, u, wdev, g.nx, g.ny, g.nz, np, zb, fz0, cz0, assign);
@@ -2798,11 +2792,7 @@ void mz_xfer_prolong(hipStream_t s, const amg_mat *A, const double *ec, const Ge
                      double omega, int mode, double *out, double *u_priv, int zlo, int zhi, int fz0, int cz0,
                      unsigned long long *stamp)
 {
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_val[j];
-   }
+   const MpSten S = mp_sten(A);
    const int P = A->mz_P;
    if (zhi < 0) zhi = g.nz;
    const int nk = zhi - zlo;
@@ -2810,23 +2800,16 @@ void mz_xfer_prolong(hipStream_t s, const amg_mat *A, const double *ec, const Ge
    const int zc = mz_chunk(A, nk, P / 512);
    const int npb = P / 512, nch = (nk + zc - 1) / zc;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
-#define AMG_XP(U, O)                                                                                           \
-   mz_xfer_prolong_kernel<U, O><<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, ec, wdev, -omega, \
-                                                          g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd, out, u_priv, \
-                                                          zlo, zhi, fz0, cz0, mode == 1 ? stamp : nullptr)
-#define AMG_XP2(U)                 \
-   if (mode == 1 && atomic_noret_mode() == 2) AMG_XP(U, 4); \
-   else if (mode == 1 && atomic_noret_mode()) AMG_XP(U, 3); \
-   else if (mode == 1) AMG_XP(U, 1); \
-   else if (mode == 2) AMG_XP(U, 2); \
-   else AMG_XP(U, 0);
-   if (A->mp_uni) {
-      AMG_XP2(true)
-   } else {
-      AMG_XP2(false)
-   }
-#undef AMG_XP2
-#undef AMG_XP
+   // the kernel's OUT: mode 1 (atomic add) as 1, or 3 / 4 with
+   // atomic_noret_mode 1 / 2; mode 2 (u + ef) as 2; otherwise 0 (ef stored)
+   const int om = mode == 1 ? (atomic_noret_mode() == 2 ? 4 : atomic_noret_mode() ? 3 : 1) : mode == 2 ? 2 : 0;
+   pick_bool(A->mp_uni, [&](auto uni) {
+      pick_int<1, 2, 3, 4>(om, otherwise<0>, [&](auto o) {
+         mz_xfer_prolong_kernel<decltype(uni)::value, decltype(o)::value><<<npb * nch, 256, 0, s>>>(
+            A->ppat, A->mpmask, A->pp_n, mv, S, ec, wdev, -omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd, out,
+            u_priv, zlo, zhi, fz0, cz0, mode == 1 ? stamp : nullptr);
+      });
+   });
 }
 
 // The same fused sweep with NL lines per workgroup (lines of nx % 512 == 0
@@ -3170,89 +3153,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
 void mz_prolong_sweep(hipStream_t s, const amg_mat *A, const double *f, const double *u, const double *ec,
                       const GeoT &g, const double *wdev, const double *l1, double omega, double *uout)
 {
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_val[j];
-   }
+   const MpSten S = mp_sten(A);
    const int P = A->mz_P, nz = A->nrows / P;
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
+   using T = std::true_type;
+   using F = std::false_type;
+   // a workgroup owns nl lines of 512 points and marches over a chunk of planes
+   auto lds = [&](auto uni, auto l1c, auto nl, auto occ) {
+      constexpr int N = decltype(nl)::value;
+      const int npb = P / (512 * N), zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
+      mz_prolong_sweep_lds_kernel<decltype(uni)::value, decltype(l1c)::value, N, decltype(occ)::value>
+         <<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, omega, g.nx, g.ny, g.nz,
+                                    zc, npb, A->ctx->mz_xcd, uout);
+   };
+   auto nlines = [&](auto uni, auto l1c, auto nl) {
+      constexpr int N = decltype(nl)::value;
+      const int npb = P / (512 * N), zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
+      mz_prolong_sweep_nl_kernel<decltype(uni)::value, decltype(l1c)::value, N><<<npb * nch, 256, 0, s>>>(
+         A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd,
+         uout);
+   };
+   auto oneline = [&](auto uni, auto l1c) {
+      const int npb = P / 512, zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
+      mz_prolong_sweep_kernel<decltype(uni)::value, decltype(l1c)::value><<<npb * nch, 256, 0, s>>>(
+         A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd,
+         uout);
+   };
+   // every form exists for uniform / per-pattern values and Jacobi / L1 Jacobi
+   auto uni_l1 = [&](auto form) {
+      pick_bool(A->mp_uni, [&](auto uni) { pick_bool(l1 != nullptr, [&](auto l1c) { form(uni, l1c); }); });
+   };
    // fuse_prolong 1: four lines per workgroup, 3: two, 2: one (mz_prolong_sweep_kernel);
    // 4 / 5: two / four lines, the coarse correction from an LDS ring (mz_prolong_sweep_lds_kernel)
    const int fp = A->ctx->fuse_prolong;
-   if (fp >= 6 && g.nx % 512 == 0 && g.ny % 2 == 0) {
-      // two lines, the kernel held to 5 / 6 waves per SIMD (register budget)
-      const int npb = P / 1024, zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
-#define AMG_PSO(U, L, O)                                                                                           \
-   mz_prolong_sweep_lds_kernel<U, L, 2, O><<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, \
-                                                                     wdev, omega, g.nx, g.ny, g.nz, zc, npb,           \
-                                                                     A->ctx->mz_xcd, uout)
-      if (A->mp_uni && !l1) {
-         if (fp == 6) AMG_PSO(true, false, 5);
-         else AMG_PSO(true, false, 6);
-         return;
-      }
-#undef AMG_PSO
+   if (fp >= 6 && g.nx % 512 == 0 && g.ny % 2 == 0 && A->mp_uni && !l1) {
+      // two lines, the kernel held to 5 (fuse_prolong 6) / 6 waves per SIMD
+      // (register budget): uniform values and plain Jacobi only
+      pick_bool(fp == 6, [&](auto six) { lds(T{}, F{}, int_c<2>{}, int_c<decltype(six)::value ? 5 : 6>{}); });
+      return;
    }
    if ((fp == 4 || fp == 5) && g.nx % 512 == 0 && g.ny % (fp == 4 ? 2 : 4) == 0) {
-      const int NLs = fp == 4 ? 2 : 4;
-      const int npb = P / (512 * NLs), zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
-#define AMG_PSL(U, L, N)                                                                                               \
-   mz_prolong_sweep_lds_kernel<U, L, N><<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, \
-                                                                  omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd, uout)
-#define AMG_PSL2(N)                           \
-   if (A->mp_uni) {                           \
-      if (l1) AMG_PSL(true, true, N);         \
-      else AMG_PSL(true, false, N);           \
-   } else {                                   \
-      if (l1) AMG_PSL(false, true, N);        \
-      else AMG_PSL(false, false, N);          \
-   }
-      if (NLs == 2) {
-         AMG_PSL2(2)
-      } else {
-         AMG_PSL2(4)
-      }
-#undef AMG_PSL2
-#undef AMG_PSL
+      pick_int<4>(fp, otherwise<5>, [&](auto f45) {
+         uni_l1([&](auto uni, auto l1c) {
+            lds(uni, l1c, int_c<decltype(f45)::value == 4 ? 2 : 4>{}, int_c<1>{});
+         });
+      });
       return;
    }
+   // fuse_prolong 6+ falls back here where its form does not apply
    const int NL = fp == 3 ? 2 : 4;
-   if (fp != 2 && g.nx % 512 == 0 && g.ny % NL == 0) {
-      const int npb = P / (512 * NL), zc = mz_chunk(A, nz, npb), nch = (nz + zc - 1) / zc;
-#define AMG_PSN(U, L, N)                                                                                              \
-   mz_prolong_sweep_nl_kernel<U, L, N><<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, \
-                                                                 omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd, uout)
-#define AMG_PSN2(N)                           \
-   if (A->mp_uni) {                           \
-      if (l1) AMG_PSN(true, true, N);         \
-      else AMG_PSN(true, false, N);           \
-   } else {                                   \
-      if (l1) AMG_PSN(false, true, N);        \
-      else AMG_PSN(false, false, N);          \
-   }
-      if (NL == 2) {
-         AMG_PSN2(2)
-      } else {
-         AMG_PSN2(4)
-      }
-#undef AMG_PSN2
-#undef AMG_PSN
-      return;
-   }
-   const int zc = mz_chunk(A, nz, P / 512);
-   const int npb = P / 512, nch = (nz + zc - 1) / zc;
-#define AMG_PS(U, L) \
-   mz_prolong_sweep_kernel<U, L><<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, mv, S, u, ec, f, l1, wdev, \
-                                                           omega, g.nx, g.ny, g.nz, zc, npb, A->ctx->mz_xcd, uout)
-   if (A->mp_uni) {
-      if (l1) AMG_PS(true, true);
-      else AMG_PS(true, false);
-   } else {
-      if (l1) AMG_PS(false, true);
-      else AMG_PS(false, false);
-   }
-#undef AMG_PS
+   if (fp != 2 && g.nx % 512 == 0 && g.ny % NL == 0)
+      pick_int<2>(NL, otherwise<4>, [&](auto nl) {
+         uni_l1([&](auto uni, auto l1c) { nlines(uni, l1c, nl); });
+      });
+   else
+      uni_l1(oneline);
 }
 
 // Geometric restriction f_c = R r (SMEM_Sync_Parfor_Restrict,
@@ -3345,18 +3300,17 @@ static void launch_dc_op(hipStream_t s, const amg_mat *A, const double *x, int r
       csr_rpp_kernel<NEG, NEED_DIAG, Epi, 2><<<(re - rb + 1023) / 1024, 256, A->pp_n * A->pp_stride * 4, s>>>(
          A->ppat, A->pptab, A->pp_n, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->pp_stride, A->danch,
          A->pp_centre0, A->pbase, A->pdelta);
-   else if (A->rpat && A->dc_maxrow <= 8)
-      csr_rp_kernel<NEG, NEED_DIAG, Epi, 4><<<(tiles + 3) / 4, 256, 0, s>>>(
-         A->rpat, A->ptab, A->rp_n, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->danch);
-   else if (A->rpat)
-      csr_rp_kernel<NEG, NEED_DIAG, Epi, 2><<<(tiles + 1) / 2, 256, 0, s>>>(
-         A->rpat, A->ptab, A->rp_n, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->danch);
-   else if (A->dc_maxrow <= 8)
-      csr_dc_kernel<NEG, NEED_DIAG, Epi, 4, true, 8><<<(tiles + 3) / 4, 256, 0, s>>>(
-         A->rowptr, A->didx, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->danch);
    else
-      csr_dc_kernel<NEG, NEED_DIAG, Epi, 2, true, AMG_DC_MAXROW><<<(tiles + 1) / 2, 256, 0, s>>>(
-         A->rowptr, A->didx, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->danch);
+      pick_bool(A->dc_maxrow <= 8, [&](auto r8) {
+         constexpr int RPL = decltype(r8)::value ? 4 : 2; // 256-row tiles per workgroup
+         if (A->rpat)
+            csr_rp_kernel<NEG, NEED_DIAG, Epi, RPL><<<(tiles + RPL - 1) / RPL, 256, 0, s>>>(
+               A->rpat, A->ptab, A->rp_n, A->doff, A->dval, x, rb, re, e, partials, A->dc_n, A->danch);
+         else
+            csr_dc_kernel<NEG, NEED_DIAG, Epi, RPL, true, decltype(r8)::value ? 8 : AMG_DC_MAXROW>
+               <<<(tiles + RPL - 1) / RPL, 256, 0, s>>>(A->rowptr, A->didx, A->doff, A->dval, x, rb, re, e, partials,
+                                                       A->dc_n, A->danch);
+      });
 }
 
 // Long-row operators (dense coarse levels of classical hierarchies: hundreds of
@@ -3542,12 +3496,19 @@ static void launch_long_cfg(hipStream_t s, const amg_mat *A, const double *x, in
                             double *partials = nullptr)
 {
    const int nb = (re - rb + RW - 1) / RW;
-   if (A->vidx)
-      csr_long_kernel<NEG, NEED_DIAG, Epi, true, TB, RW><<<nb, TB, 0, s>>>(A->rowptr, A->col, A->val, A->vidx,
-                                                                          A->vtab, x, rb, re, e, partials);
-   else
-      csr_long_kernel<NEG, NEED_DIAG, Epi, false, TB, RW><<<nb, TB, 0, s>>>(A->rowptr, A->col, A->val, nullptr,
-                                                                           nullptr, x, rb, re, e, partials);
+   pick_bool(A->vidx != nullptr, [&](auto vi) {
+      constexpr bool VI = decltype(vi)::value;
+      csr_long_kernel<NEG, NEED_DIAG, Epi, VI, TB, RW><<<nb, TB, 0, s>>>(
+         A->rowptr, A->col, A->val, VI ? A->vidx : nullptr, VI ? A->vtab : nullptr, x, rb, re, e, partials);
+   });
+}
+
+// AMG_LONG_RW=128 / 256: rows per workgroup on the largest levels (the rows'
+// sequential sums then spread over 2 / 4 waves instead of one)
+static int knob_long_rw()
+{
+   static const int v = env_int("AMG_LONG_RW", 0);
+   return v;
 }
 
 // rows per workgroup: the most that still gives >= 4096 workgroups (64 .. 8);
@@ -3562,41 +3523,28 @@ static void launch_long(hipStream_t s, const amg_mat *A, const double *x, int rb
       // with norm partials 64 (one 256-row tile per workgroup)
       const int rpw = partials ? 64 : n >= 256 * 4096 ? 64 : n >= 128 * 4096 ? 32 : n >= 64 * 4096 ? 16 : 8;
       const int nb = (int)(((long long)n + 4 * rpw - 1) / (4 * rpw));
-      auto go = [&](auto cw) {
-         constexpr int W = decltype(cw)::value;
-         if (A->vidx)
-            csr_longw_kernel<NEG, NEED_DIAG, Epi, true, W><<<nb, 256, 0, s>>>(
-               A->rowptr, A->col, A->val, A->vidx, A->vtab, x, rb, re, rpw, A->ctx->long_xcd, e, partials);
-         else
-            csr_longw_kernel<NEG, NEED_DIAG, Epi, false, W><<<nb, 256, 0, s>>>(
-               A->rowptr, A->col, A->val, nullptr, nullptr, x, rb, re, rpw, A->ctx->long_xcd, e, partials);
-      };
-      if (A->ctx->long_form == 2)
-         go(std::integral_constant<int, 16>{});
-      else
-         go(std::integral_constant<int, 8>{});
+      // long_form 2: 16 entries per lane and chunk, otherwise 8
+      pick_int<2>(A->ctx->long_form, otherwise<1>, [&](auto lf) {
+         pick_bool(A->vidx != nullptr, [&](auto vi) {
+            constexpr bool VI = decltype(vi)::value;
+            csr_longw_kernel<NEG, NEED_DIAG, Epi, VI, decltype(lf)::value == 2 ? 16 : 8><<<nb, 256, 0, s>>>(
+               A->rowptr, A->col, A->val, VI ? A->vidx : nullptr, VI ? A->vtab : nullptr, x, rb, re, rpw,
+               A->ctx->long_xcd, e, partials);
+         });
+      });
       return;
    }
-   // AMG_LONG_RW=128 / 256: rows per workgroup on the largest levels (the rows'
-   // sequential sums then spread over 2 / 4 waves instead of one)
-   static const int lrw = [] {
-      const char *v = std::getenv("AMG_LONG_RW");
-      return v ? std::atoi(v) : 0;
-   }();
-   if (partials)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 256>(s, A, x, rb, re, e, partials);
-   else if (lrw == 256 && n >= 256 * 2048)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 256>(s, A, x, rb, re, e);
-   else if (lrw == 128 && n >= 128 * 2048)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 128>(s, A, x, rb, re, e);
-   else if (n >= 64 * 4096)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 64>(s, A, x, rb, re, e);
-   else if (n >= 32 * 4096)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 32>(s, A, x, rb, re, e);
-   else if (n >= 16 * 4096)
-      launch_long_cfg<NEG, NEED_DIAG, 256, 16>(s, A, x, rb, re, e);
-   else
-      launch_long_cfg<NEG, NEED_DIAG, 256, 8>(s, A, x, rb, re, e);
+   const int lrw = knob_long_rw();
+   const int rw = partials                          ? 256
+                  : lrw == 256 && n >= 256 * 2048   ? 256
+                  : lrw == 128 && n >= 128 * 2048   ? 128
+                  : n >= 64 * 4096                  ? 64
+                  : n >= 32 * 4096                  ? 32
+                  : n >= 16 * 4096                  ? 16
+                                                    : 8;
+   pick_int<256, 128, 64, 32, 16>(rw, otherwise<8>, [&](auto rwc) {
+      launch_long_cfg<NEG, NEED_DIAG, 256, decltype(rwc)::value>(s, A, x, rb, re, e, partials);
+   });
 }
 
 // production configuration (tools/tune_spmv.py picks it on the MI355X)
@@ -3624,6 +3572,7 @@ __device__ __forceinline__ void st2(double *p, v2d v, int nt)
 }
 
 struct EpiGemv {
+   static constexpr bool short_cfg = true; // launch_row_op: ShortCfg tiles on short value-indexed rows
    const double *b;
    double *y;
    int imode;
@@ -3726,6 +3675,7 @@ __device__ __forceinline__ double jac_div1(double num, double a, double dq, doub
 // Jacobi sweep epilogue (SMEM_Smooth.cpp:35-45): res = f - sum; u_new = u + w*res/a
 // (dq, rq: a uniform diagonal and its reciprocal, jac_div2; dq = 0: off)
 struct EpiJacobi {
+   static constexpr bool short_cfg = true; // launch_row_op: ShortCfg tiles on short value-indexed rows
    const double *f;
    const double *x;
    double *out;
@@ -3754,6 +3704,7 @@ struct EpiJacobi {
 
 // L1 Jacobi sweep epilogue (SMEM_Smooth.cpp:122-130): u_new = u + res/l1
 struct EpiL1Jacobi {
+   static constexpr bool short_cfg = false; // launch_row_op: never ShortCfg tiles (not measured; ProdCfg on every row length)
    const double *f;
    const double *x;
    const double *l1;
@@ -3783,6 +3734,7 @@ struct EpiL1Jacobi {
 // u_next = u + w*r/a_ii (L1: u + r/l1).  Writes r and u_next, returns r for
 // the norm.
 struct EpiResJacobi {
+   static constexpr bool short_cfg = true; // launch_row_op: ShortCfg tiles on short value-indexed rows
    const double *f;
    const double *x;
    const double *l1;
@@ -4021,11 +3973,7 @@ static bool fast_div_of(const amg_mat *A, double *d, double *y);
 void mz_sweep_outer(hipStream_t s, const amg_mat *A, const double *f, const double *u, double *u1out,
                     double *rout, double *unext, double omega, double *partials)
 {
-   MpSten Sv;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      Sv.off[j] = A->mp_off[j];
-      Sv.val[j] = A->mp_val[j];
-   }
+   const MpSten Sv = mp_sten(A);
    const int P = A->mz_P, nz = A->nrows / P;
    const int npb = P / (512 * AMG_MZF_NL);
    int zc = std::max(1, std::min(A->ctx->mz_zc, AMG_MZ_MAXZC));
@@ -4043,29 +3991,15 @@ void mz_sweep_outer(hipStream_t s, const amg_mat *A, const double *f, const doub
    }();
    double dq = 0.0, rq = 0.0;
    if (!fast_div_of(A, &dq, &rq)) dq = rq = 0.0;
-   auto go = [&](auto store, auto minb) {
-      constexpr bool ST = decltype(store)::value;
-      constexpr int MB = decltype(minb)::value;
-      if (pd == 2)
-         mz_sweep_outer_kernel<ST, MB, 2><<<npb * nch, 256 * AMG_MZF_NT, 0, s>>>(
-            A->ppat, A->mpmask, A->pp_n, Sv, f, u, u1out, rout, unext, omega, P, nz, zc, npb, A->ctx->mz_xcd,
-            partials, dq, rq);
-      else
-         mz_sweep_outer_kernel<ST, MB, 1><<<npb * nch, 256 * AMG_MZF_NT, 0, s>>>(
-            A->ppat, A->mpmask, A->pp_n, Sv, f, u, u1out, rout, unext, omega, P, nz, zc, npb, A->ctx->mz_xcd,
-            partials, dq, rq);
-   };
-   using T = std::true_type;
-   using F = std::false_type;
-   using M1 = std::integral_constant<int, 1>;
-   using M2 = std::integral_constant<int, 2>;
-   if (u1out) {
-      if (occ2) go(T{}, M2{});
-      else go(T{}, M1{});
-   } else {
-      if (occ2) go(F{}, M2{});
-      else go(F{}, M1{});
-   }
+   pick_bool(u1out != nullptr, [&](auto store) {
+      pick_int<2>(occ2 ? 2 : 1, otherwise<1>, [&](auto minb) {
+         pick_int<2>(pd, otherwise<1>, [&](auto pdc) {
+            mz_sweep_outer_kernel<decltype(store)::value, decltype(minb)::value, decltype(pdc)::value>
+               <<<npb * nch, 256 * AMG_MZF_NT, 0, s>>>(A->ppat, A->mpmask, A->pp_n, Sv, f, u, u1out, rout, unext, omega,
+                                                       P, nz, zc, npb, A->ctx->mz_xcd, partials, dq, rq);
+         });
+      });
+   });
 }
 
 __device__ __forceinline__ const double *epi_pf_vec(const EpiJacobi &e) { return e.x; }
@@ -4291,74 +4225,55 @@ __global__ __launch_bounds__(256) void bsr3_kernel(const long long *__restrict__
    epi.finish(i, acc, a, (pf_is_x<Epi>::value && epi_pf_vec(epi) == x) ? xi : epi.pf(i));
 }
 
+// AMG_BSR3_RU: blocks per batch of in-flight loads of the lane-per-block-row
+// form (2, 4, 6 (default: 212 against 219 us for 4 at r = 6,
+// profiles/r05/bsr3/ru/) or 8)
+static int knob_bsr3_ru()
+{
+   static const int v = env_int("AMG_BSR3_RU", 6);
+   return v;
+}
+// AMG_BSR3_U: the same for the shared-x value-indexed 21-row slices (2, 3, 4,
+// 6, 9, 14 or 27; default 4: occupancy over loads in flight, 0.425 against
+// 0.40 at 9, r = 5)
+static int knob_bsr3_u()
+{
+   static const int v = env_int("AMG_BSR3_U", 4);
+   return v;
+}
+
 template <int NEG, bool NEED_DIAG, class Epi>
 static void launch_bsr3(hipStream_t s, const amg_mat *A, const double *x, int rb, int re, const Epi &e)
 {
    const int t0 = rb / 3, t1 = re / 3;
    if (A->bsl == 64) {
-      // a lane per block row (value-indexed 64-row slices); AMG_BSR3_RU: blocks
-      // per batch of in-flight loads (2, 4, 6 (default: 212 against 219 us for 4
-      // at r = 6, profiles/r05/bsr3/ru/) or 8)
-      static const int ru = [] {
-         const char *v = std::getenv("AMG_BSR3_RU");
-         return v ? std::atoi(v) : 6;
-      }();
+      // a lane per block row (value-indexed 64-row slices)
       const int nsl = (t1 - t0 + 63) / 64;
-#define AMG_BR(UU)                                                                                            \
-   bsr3_row_kernel<NEG, NEED_DIAG, Epi, UU><<<(nsl + 3) / 4, 256, 0, s>>>(A->soff, A->bcol, A->bdiag, A->bmode, \
-                                                                          A->bvi, A->vtab, A->rowptr, A->col,    \
-                                                                          A->val, x, t0, t1, e)
-      if (ru == 2) AMG_BR(2);
-      else if (ru == 4) AMG_BR(4);
-      else if (ru == 8) AMG_BR(8);
-      else AMG_BR(6);
-#undef AMG_BR
+      pick_int<2, 4, 8>(knob_bsr3_ru(), otherwise<6>, [&](auto ru) {
+         bsr3_row_kernel<NEG, NEED_DIAG, Epi, decltype(ru)::value><<<(nsl + 3) / 4, 256, 0, s>>>(
+            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
+      });
       return;
    }
    const int nsl = (t1 - t0 + 20) / 21;
    const int nb = (nsl + 3) / 4;
-   // ctx->bsr3_xs: the node's x shared across the block row's three lanes;
-   // AMG_BSR3_U: blocks per batch of in-flight loads (2, 3, 4, 6, 9, 14 or 27)
-   const bool xs = A->ctx->bsr3_xs != 0;
-   static const int ub = [] {
-      const char *v = std::getenv("AMG_BSR3_U");
-      return v ? std::atoi(v) : 4; // 4: occupancy over loads in flight (0.425 against 0.40 at 9, r = 5)
-   }();
-   if (A->bsr3 == 1) {
-      if (xs && ub == 3)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 3><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs && ub == 2)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 2><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs && ub == 6)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 6><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs && ub == 4)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 4><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs && ub == 27)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 27><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs && ub == 14)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true, 14><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else if (xs)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true, true><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, A->bvi, nullptr, A->vtab, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else
-         bsr3_kernel<NEG, NEED_DIAG, Epi, true><<<nb, 256, 0, s>>>(A->soff, A->bcol, A->bdiag, A->bmode, A->bvi,
-                                                                    nullptr, A->vtab, A->rowptr, A->col, A->val, x,
-                                                                    t0, t1, e);
-   } else {
-      if (xs)
-         bsr3_kernel<NEG, NEED_DIAG, Epi, false, true><<<nb, 256, 0, s>>>(
-            A->soff, A->bcol, A->bdiag, A->bmode, nullptr, A->bval, nullptr, A->rowptr, A->col, A->val, x, t0, t1, e);
-      else
-         bsr3_kernel<NEG, NEED_DIAG, Epi, false><<<nb, 256, 0, s>>>(A->soff, A->bcol, A->bdiag, A->bmode, nullptr,
-                                                                     A->bval, nullptr, A->rowptr, A->col, A->val, x,
-                                                                     t0, t1, e);
-   }
+   // A->bsr3 == 1: value-indexed blocks (bvi + vtab), otherwise fp64 (bval);
+   // ctx->bsr3_xs: the node's x shared across the block row's three lanes
+   pick_bool(A->bsr3 == 1, [&](auto vi) {
+      pick_bool(A->ctx->bsr3_xs != 0, [&](auto xs) {
+         constexpr bool VI = decltype(vi)::value, XS = decltype(xs)::value;
+         auto run = [&](auto u) {
+            bsr3_kernel<NEG, NEED_DIAG, Epi, VI, XS, decltype(u)::value><<<nb, 256, 0, s>>>(
+               A->soff, A->bcol, A->bdiag, A->bmode, VI ? A->bvi : nullptr, VI ? nullptr : A->bval,
+               VI ? A->vtab : nullptr, A->rowptr, A->col, A->val, x, t0, t1, e);
+         };
+         // only the value-indexed shared-x form has batches other than 9
+         if constexpr (VI && XS)
+            pick_int<2, 3, 4, 6, 14, 27>(knob_bsr3_u(), otherwise<9>, run);
+         else
+            run(int_c<9>{});
+      });
+   });
 }
 
 // the block form serves row ranges that start on a slice (21 or 64 block rows)
@@ -4369,6 +4284,49 @@ static inline bool use_bsr3(const amg_mat *A, int rb, int re, const double *part
    return A->bsr3 && !partials && rb % sr == 0 && (re % sr == 0 || re == A->nrows) && A->nrows % 3 == 0;
 }
 
+// The storage-format ladder of the row operators (SpGEMV, Jacobi, L1 Jacobi,
+// residual + Jacobi; DESIGN.md §4 has the operator x rung table): 3x3 blocks,
+// dictionary / pattern / march forms (launch_dc_op), long rows, then the tile
+// kernels.  What differs between the operators is a property of the call or
+// of the epilogue, each a measured decision:
+//   PTILE            persistent short tiles, SpGEMV without negation only
+//   Epi::short_cfg   ShortCfg tiles on short value-indexed rows (not L1 Jacobi)
+template <int NEG, bool NEED_DIAG, bool PTILE = false, class Epi>
+static void launch_row_op(hipStream_t s, const amg_mat *A, const double *x, int rb, int re, const Epi &e,
+                          double *partials)
+{
+   const int nb = tile_blocks(rb, re);
+   if (use_bsr3(A, rb, re, partials))
+      launch_bsr3<NEG, NEED_DIAG>(s, A, x, rb, re, e);
+   else if (A->didx)
+      launch_dc_op<NEG, NEED_DIAG>(s, A, x, rb, re, e, partials, nb);
+   else if (long_rows(A))
+      launch_long<NEG, NEED_DIAG>(s, A, x, rb, re, e, partials);
+   else if (!A->vidx)
+      csr_tile_kernel<ProdCfg, NEG, NEED_DIAG, Epi>
+         <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, partials);
+   else {
+      if constexpr (PTILE)
+         if (!partials && A->nnz < 5LL * A->nrows && nb > 4096) {
+            // short rows (prolongation): tiles carry little work, so 4096 persistent
+            // workgroups walking the tiles beat one workgroup per tile
+            csr_ptile_kernel<ShortCfg, NEG, NEED_DIAG, Epi, true><<<4096, 256, 0, s>>>(
+               A->rowptr, A->col, A->val, x, rb, re, e, nullptr, A->vidx, A->vtab, nb);
+            return;
+         }
+      if constexpr (Epi::short_cfg)
+         if (short_rows(A)) {
+            csr_tile_kernel<ShortCfg, NEG, NEED_DIAG, Epi, true><<<nb, 256, 0, s>>>(
+               A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
+            return;
+         }
+      csr_tile_kernel<ProdCfg, NEG, NEED_DIAG, Epi, true><<<nb, 256, 0, s>>>(
+         A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
+   }
+}
+
+// r = b - A x: fused on the dictionary rung only (launch_dc_op directly, so
+// no other form is instantiated for EpiFsub); elsewhere y = A x, then r = b - y
 void residual_fsub(hipStream_t s, const amg_mat *A, const double *x, const double *b, double *y, double *r, int n)
 {
    if (n <= 0) return;
@@ -4384,48 +4342,11 @@ void spgemv(hipStream_t s, const amg_mat *A, const double *x, const double *b, c
             double *y, int rb, int re, double *partials)
 {
    if (re <= rb) return;
-   EpiGemv e{b, y, g.init, g.scale, g.alpha, g.temp};
-   const int nb = tile_blocks(rb, re);
-   if (use_bsr3(A, rb, re, partials)) {
-      if (g.negacc)
-         launch_bsr3<1, false>(s, A, x, rb, re, e);
-      else
-         launch_bsr3<0, false>(s, A, x, rb, re, e);
-   } else if (A->didx) {
-      if (g.negacc)
-         launch_dc_op<1, false>(s, A, x, rb, re, e, partials, nb);
-      else
-         launch_dc_op<0, false>(s, A, x, rb, re, e, partials, nb);
-   } else if (long_rows(A)) {
-      if (g.negacc)
-         launch_long<1, false>(s, A, x, rb, re, e, partials);
-      else
-         launch_long<0, false>(s, A, x, rb, re, e, partials);
-   } else if (A->vidx && !partials && !g.negacc && A->nnz < 5LL * A->nrows && nb > 4096) {
-      // short rows (prolongation): tiles carry little work, so 4096 persistent
-      // workgroups walking the tiles beat one workgroup per tile
-      csr_ptile_kernel<ShortCfg, 0, false, EpiGemv, true><<<4096, 256, 0, s>>>(
-         A->rowptr, A->col, A->val, x, rb, re, e, nullptr, A->vidx, A->vtab, nb);
-   } else if (A->vidx && short_rows(A)) {
-      if (g.negacc)
-         csr_tile_kernel<ShortCfg, 1, false, EpiGemv, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ShortCfg, 0, false, EpiGemv, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-   } else if (A->vidx) {
-      if (g.negacc)
-         csr_tile_kernel<ProdCfg, 1, false, EpiGemv, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ProdCfg, 0, false, EpiGemv, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-   } else if (g.negacc)
-      csr_tile_kernel<ProdCfg, 1, false, EpiGemv>
-         <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, partials);
+   const EpiGemv e{b, y, g.init, g.scale, g.alpha, g.temp};
+   if (g.negacc)
+      launch_row_op<1, false>(s, A, x, rb, re, e, partials);
    else
-      csr_tile_kernel<ProdCfg, 0, false, EpiGemv>
-         <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, partials);
+      launch_row_op<0, false, /*PTILE*/ true>(s, A, x, rb, re, e, partials);
 }
 
 // a marched operator's uniform diagonal d whose reciprocal divides exactly
@@ -4460,52 +4381,14 @@ void jacobi_sweep(hipStream_t s, const amg_mat *A, const double *f, const double
                   const double *l1, double omega, double *out, int rb, int re)
 {
    if (re <= rb) return;
-   const int nb = tile_blocks(rb, re);
-   if (use_bsr3(A, rb, re, nullptr)) {
-      if (l1)
-         launch_bsr3<1, false>(s, A, x, rb, re, EpiL1Jacobi{f, x, l1, out});
-      else {
-         EpiJacobi e{f, x, out, omega};
-         fast_div_of(A, &e.dq, &e.rq);
-         launch_bsr3<1, true>(s, A, x, rb, re, e);
-      }
-   } else if (A->didx) {
-      if (l1)
-         launch_dc_op<1, false>(s, A, x, rb, re, EpiL1Jacobi{f, x, l1, out}, nullptr, nb);
-      else {
-         EpiJacobi e{f, x, out, omega, stream_hint(A)};
-         fast_div_of(A, &e.dq, &e.rq);
-         launch_dc_op<1, true>(s, A, x, rb, re, e, nullptr, nb);
-      }
-   } else if (long_rows(A)) {
-      if (l1)
-         launch_long<1, false>(s, A, x, rb, re, EpiL1Jacobi{f, x, l1, out});
-      else {
-         EpiJacobi e{f, x, out, omega};
-         fast_div_of(A, &e.dq, &e.rq);
-         launch_long<1, true>(s, A, x, rb, re, e);
-      }
-   } else if (l1) {
-      EpiL1Jacobi e{f, x, l1, out};
-      if (A->vidx)
-         csr_tile_kernel<ProdCfg, 1, false, EpiL1Jacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, nullptr, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ProdCfg, 1, false, EpiL1Jacobi>
-            <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, nullptr);
-   } else {
-      EpiJacobi e{f, x, out, omega};
-      fast_div_of(A, &e.dq, &e.rq);
-      if (A->vidx && short_rows(A))
-         csr_tile_kernel<ShortCfg, 1, true, EpiJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, nullptr, A->vidx, A->vtab);
-      else if (A->vidx)
-         csr_tile_kernel<ProdCfg, 1, true, EpiJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, nullptr, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ProdCfg, 1, true, EpiJacobi>
-            <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, nullptr);
+   if (l1) {
+      launch_row_op<1, false>(s, A, x, rb, re, EpiL1Jacobi{f, x, l1, out}, nullptr);
+      return;
    }
+   // the streaming hint only where the dictionary rung takes the launch
+   EpiJacobi e{f, x, out, omega, A->didx && !use_bsr3(A, rb, re, nullptr) ? stream_hint(A) : 0};
+   fast_div_of(A, &e.dq, &e.rq);
+   launch_row_op<1, true>(s, A, x, rb, re, e, nullptr);
 }
 
 void residual_jacobi(hipStream_t s, const amg_mat *A, const double *f, const double *x,
@@ -4513,45 +4396,15 @@ void residual_jacobi(hipStream_t s, const amg_mat *A, const double *f, const dou
                      double *partials)
 {
    if (re <= rb) return;
-   const int nb = tile_blocks(rb, re);
    EpiResJacobi e{f, x, l1, r, unext, omega};
+   // the streaming hint on every dictionary-coded matrix, the block rung included
    if (A->didx) e.nt = stream_hint(A);
    fast_div_of(A, &e.dq, &e.rq);
-   if (use_bsr3(A, rb, re, partials)) {
-      if (l1)
-         launch_bsr3<1, false>(s, A, x, rb, re, e);
-      else
-         launch_bsr3<1, true>(s, A, x, rb, re, e);
-   } else if (A->didx) {
-      if (l1)
-         launch_dc_op<1, false>(s, A, x, rb, re, e, partials, nb);
-      else
-         launch_dc_op<1, true>(s, A, x, rb, re, e, partials, nb);
-   } else if (long_rows(A)) {
-      if (l1)
-         launch_long<1, false>(s, A, x, rb, re, e, partials);
-      else
-         launch_long<1, true>(s, A, x, rb, re, e, partials);
-   } else if (A->vidx && short_rows(A)) {
-      if (l1)
-         csr_tile_kernel<ShortCfg, 1, false, EpiResJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ShortCfg, 1, true, EpiResJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-   } else if (A->vidx) {
-      if (l1)
-         csr_tile_kernel<ProdCfg, 1, false, EpiResJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-      else
-         csr_tile_kernel<ProdCfg, 1, true, EpiResJacobi, true><<<nb, 256, 0, s>>>(
-            A->rowptr, A->col, A->val, x, rb, re, e, partials, A->vidx, A->vtab);
-   } else if (l1)
-      csr_tile_kernel<ProdCfg, 1, false, EpiResJacobi>
-         <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, partials);
+   // the L1 form divides by l1, not the diagonal
+   if (l1)
+      launch_row_op<1, false>(s, A, x, rb, re, e, partials);
    else
-      csr_tile_kernel<ProdCfg, 1, true, EpiResJacobi>
-         <<<nb, 256, 0, s>>>(A->rowptr, A->col, A->val, x, rb, re, e, partials);
+      launch_row_op<1, true>(s, A, x, rb, re, e, partials);
 }
 
 // ---------------------------------------------------------------------------
@@ -4640,11 +4493,7 @@ template <int FORM, int RPL, int OP, int NT = 0>
 static void launch_mp_tune(hipStream_t s, const amg_mat *A, const double *x, double *y)
 {
    if (!A->mp_J || !A->mp_uni || A->mp_J > 8) return;
-   MpSten S;
-   for (int j = 0; j < AMG_MP_MAXJ; j++) {
-      S.off[j] = A->mp_off[j];
-      S.val[j] = A->mp_val[j];
-   }
+   const MpSten S = mp_sten(A);
    const int nb = (A->nrows + 512 * RPL - 1) / (512 * RPL);
    const v2d *mv = reinterpret_cast<const v2d *>(A->mpval);
    if (OP == 2) {
@@ -5883,6 +5732,19 @@ void row_max(hipStream_t s, const amg_mat *A, int *d_out)
    row_max_k<<<std::max(1, std::min(1024, (n + 255) / 256)), 256, 0, s>>>(A->rowptr, n, d_out);
 }
 
+// AMG_JGS_TILE_OCC=4: the tile form's registers capped for two workgroups per CU
+static int knob_jgs_tile_occ()
+{
+   static const int v = env_int("AMG_JGS_TILE_OCC", 1);
+   return v;
+}
+// AMG_JGS_WPE=6 / 8: the group form's registers capped for 6 / 8 waves per SIMD
+static int knob_jgs_wpe()
+{
+   static const int v = env_int("AMG_JGS_WPE", 0);
+   return v;
+}
+
 bool hybrid_jgs(hipStream_t s, const amg_mat *A, const double *f, double *u, const double *u_prev,
                 const int *d_blk, int nblk, const double *diag_scale, double weight, int zero,
                 int reverse, double *apply_u, double *apply_priv, unsigned long long *stamp)
@@ -5890,32 +5752,25 @@ bool hybrid_jgs(hipStream_t s, const amg_mat *A, const double *f, double *u, con
    if (nblk <= 0) return false;
    int mode = A->ctx->jgs_wave;
    if (mode == 3) {
-      // short rows: passes of 16 rows per block, 4 tail slots; longer rows
-      // (27-pt, classical): passes of 4 rows, 16 slots
+      // short rows: passes of 16 rows per block, 4 tail slots, 512 threads;
+      // longer rows (27-pt, classical): passes of 4 rows, 16 slots, 256 threads
       const int nwg = (nblk + 63) / 64;
-#define JGS_TILE(CH, TM, V, SH, OC)                                                                                  \
-   hybrid_jgs_tile_k<64, CH, TM, V, SH, SH ? 512 : 256, OC><<<nwg, SH ? 512 : 256, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev, \
-                                                        d_blk, nblk, diag_scale, weight, zero, reverse, apply_u,  \
-                                                        apply_priv, apply_u ? stamp : nullptr)
-      const bool vi = A->vidx != nullptr;
-      if (A->maxrow >= 0 && A->maxrow <= 8) {
-         // AMG_JGS_TILE_OCC=4: registers capped for two workgroups per CU
-         static const int occ = [] {
-            const char *v = std::getenv("AMG_JGS_TILE_OCC");
-            return v ? std::atoi(v) : 1;
-         }();
-         if (occ == 4) {
-            if (vi) JGS_TILE(16, 4, true, true, 4);
-            else JGS_TILE(16, 4, false, true, 4);
-         } else {
-            if (vi) JGS_TILE(16, 4, true, true, 1);
-            else JGS_TILE(16, 4, false, true, 1);
-         }
-      } else {
-         if (vi) JGS_TILE(4, 16, true, false, 1);
-         else JGS_TILE(4, 16, false, false, 1);
-      }
-#undef JGS_TILE
+      pick_bool(A->vidx != nullptr, [&](auto vi) {
+         pick_bool(A->maxrow >= 0 && A->maxrow <= 8, [&](auto sh) {
+            constexpr bool SH = decltype(sh)::value;
+            auto run = [&](auto occ) {
+               hybrid_jgs_tile_k<64, SH ? 16 : 4, SH ? 4 : 16, decltype(vi)::value, SH, SH ? 512 : 256,
+                                 decltype(occ)::value><<<nwg, SH ? 512 : 256, 0, s>>>(
+                  A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev, d_blk, nblk, diag_scale, weight, zero,
+                  reverse, apply_u, apply_priv, apply_u ? stamp : nullptr);
+            };
+            // the register cap (AMG_JGS_TILE_OCC=4) exists for short rows only
+            if constexpr (SH)
+               pick_int<4>(knob_jgs_tile_occ(), otherwise<1>, run);
+            else
+               run(int_c<1>{});
+         });
+      });
       return apply_u != nullptr;
    }
    // small levels (fewer workgroups than CUs) are latency-bound: jgs_small 1
@@ -5925,54 +5780,39 @@ bool hybrid_jgs(hipStream_t s, const amg_mat *A, const double *f, double *u, con
    if (mode == 1 && small && small_form == 1) mode = 2;
    if (mode == 1 && small && small_form == 2) {
       const int nwg = (nblk + 7) / 8;
-      if (A->vidx)
-         hybrid_jgs_grp_k<8, 32, true, true><<<nwg, 64, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u,
-                                                                 u_prev, d_blk, nblk, diag_scale, weight, zero, reverse);
-      else
-         hybrid_jgs_grp_k<8, 32, false, true><<<nwg, 64, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u,
-                                                                  u_prev, d_blk, nblk, diag_scale, weight, zero,
-                                                                  reverse);
+      pick_bool(A->vidx != nullptr, [&](auto vi) {
+         hybrid_jgs_grp_k<8, 32, decltype(vi)::value, true><<<nwg, 64, 0, s>>>(
+            A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev, d_blk, nblk, diag_scale, weight, zero, reverse);
+      });
       return false;
    }
    if (mode == 1 && A->maxrow >= 1 && A->maxrow <= 32) {
       // 8 lanes per block, 8 blocks per wave
       const int nwg = (nblk + 7) / 8;
-      const bool vi = A->vidx != nullptr;
-#define JGS_GRP(R, V)                                                                                               \
-   hybrid_jgs_grp_k<8, R, V><<<nwg, 64, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev, d_blk, \
-                                                nblk, diag_scale, weight, zero, reverse, apply_u, apply_priv,     \
-                                                apply_u ? stamp : nullptr)
-      // AMG_JGS_WPE=6 / 8: registers capped for 6 / 8 waves per SIMD (rows of <= 8 entries)
-      static const int jwpe = [] {
-         const char *v = std::getenv("AMG_JGS_WPE");
-         return v ? std::atoi(v) : 0;
-      }();
-      if (A->maxrow <= 8 && vi && jwpe == 8) {
-         hybrid_jgs_grp_k<8, 8, true, false, 8><<<nwg, 64, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev,
-                                                                  d_blk, nblk, diag_scale, weight, zero, reverse, apply_u,
-                                                                  apply_priv, apply_u ? stamp : nullptr);
-      } else if (A->maxrow <= 8 && vi && jwpe == 6) {
-         hybrid_jgs_grp_k<8, 8, true, false, 6><<<nwg, 64, 0, s>>>(A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev,
-                                                                  d_blk, nblk, diag_scale, weight, zero, reverse, apply_u,
-                                                                  apply_priv, apply_u ? stamp : nullptr);
-      } else if (A->maxrow <= 8) {
-         if (vi) JGS_GRP(8, true);
-         else JGS_GRP(8, false);
-      } else {
-         if (vi) JGS_GRP(32, true);
-         else JGS_GRP(32, false);
-      }
-#undef JGS_GRP
+      pick_bool(A->vidx != nullptr, [&](auto vi) {
+         pick_bool(A->maxrow <= 8, [&](auto r8) {
+            constexpr bool VI = decltype(vi)::value;
+            constexpr int R = decltype(r8)::value ? 8 : 32;
+            auto run = [&](auto wpe) {
+               hybrid_jgs_grp_k<8, R, VI, false, decltype(wpe)::value><<<nwg, 64, 0, s>>>(
+                  A->rowptr, A->col, A->val, A->vidx, A->vtab, f, u, u_prev, d_blk, nblk, diag_scale, weight, zero,
+                  reverse, apply_u, apply_priv, apply_u ? stamp : nullptr);
+            };
+            // the register caps (AMG_JGS_WPE) exist for value-indexed rows of <= 8 entries only
+            if constexpr (VI && R == 8)
+               pick_int<6, 8>(knob_jgs_wpe(), otherwise<0>, run);
+            else
+               run(int_c<0>{});
+         });
+      });
       return apply_u != nullptr;
    }
    if (mode == 2 && A->maxrow >= 0 && A->maxrow <= 32) {
       const int nwg = (nblk + 3) / 4;
-      if (A->maxrow <= 8)
-         hybrid_jgs_wave_k<8><<<nwg, 256, 0, s>>>(A->rowptr, A->col, A->val, f, u, u_prev, d_blk, nblk, diag_scale,
-                                                  weight, zero, reverse);
-      else
-         hybrid_jgs_wave_k<32><<<nwg, 256, 0, s>>>(A->rowptr, A->col, A->val, f, u, u_prev, d_blk, nblk,
-                                                   diag_scale, weight, zero, reverse);
+      pick_bool(A->maxrow <= 8, [&](auto r8) {
+         hybrid_jgs_wave_k<decltype(r8)::value ? 8 : 32><<<nwg, 256, 0, s>>>(
+            A->rowptr, A->col, A->val, f, u, u_prev, d_blk, nblk, diag_scale, weight, zero, reverse);
+      });
       return false;
    }
    const int tpb = 64;
