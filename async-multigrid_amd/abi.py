@@ -127,6 +127,7 @@ PROTOTYPES = {
     "amg_matvec_timed": (_i, [_p, _p, _p, _p, _i, _dp]),
     "amg_stream_triad": (_i, [_p, _ll, _i, _dp]),
     "amg_pmc_calib": (_i, [_p, _i, _ll]),
+    "amg_async_turns_probe": (_i, [_i, _i, _i, _i, _i, _i, _dp, _dp, _ip, _ip, _ip, _i, _ip, _ip]),
     "amg_residual": (_i, [_p, _p, _p, _p, _p, _p, _i, _i]),
     "amg_jacobi": (_i, [_p, _p, _p, _p, _p, _d, _i, _i, _i, _i, _i]),
     "amg_l1_jacobi": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i]),

@@ -8,7 +8,7 @@
 #include <mutex>
 #include <vector>
 
-#include "amg_internal.h"
+#include "amg_async.h"
 
 #include <csignal>
 #include <execinfo.h>
@@ -1465,21 +1465,12 @@ extern "C" int amg_matvec_timed(amg_ctx *c, const amg_mat *A, const amg_vec *x, 
 {
    AMG_ARG(c && A && x && y && ms && reps >= 1, "amg_matvec_timed: bad argument");
    AMG_ARG(x->n >= A->ncols && y->n >= A->nrows, "amg_matvec_timed: vector sizes");
-   hipEvent_t a, b;
-   AMG_HIP(hipEventCreate(&a));
-   AMG_HIP(hipEventCreate(&b));
    const amgk::Gemv g = amgk::gemv_mode(1.0, 0.0);
-   AMG_HIP(hipEventRecord(a, c->stream));
-   for (int r = 0; r < reps; r++)
+   auto spmv = [&] {
       amgk::spgemv(c->stream, A, x->d, nullptr, g, y->d, 0, A->nrows, nullptr);
-   AMG_HIP(hipEventRecord(b, c->stream));
-   AMG_HIP(hipEventSynchronize(b));
-   float t = 0.f;
-   AMG_HIP(hipEventElapsedTime(&t, a, b));
-   hipEventDestroy(a);
-   hipEventDestroy(b);
-   *ms = (double)t / reps;
-   return AMG_OK;
+      return AMG_OK;
+   };
+   return amg_timed_reps(c->stream, reps, spmv, ms);
 }
 
 // measurement helpers (declared in the header): PMC calibration streams
@@ -1507,28 +1498,24 @@ extern "C" int amg_stream_triad(amg_ctx *c, long long n, int reps, double *gbs)
       hipFree(b);
       return amg_set_error(AMG_ERR_OOM, "amg_stream_triad: %lld doubles", n);
    }
-   hipEvent_t e0, e1;
-   hipEventCreate(&e0);
-   hipEventCreate(&e1);
    hipMemsetAsync(b, 0, (size_t)n * 8, c->stream);
    hipMemsetAsync(d, 0, (size_t)n * 8, c->stream);
-   amgk::stream_triad(c->stream, a, b, d, 3.0, n); // warm
-   float best = 1e30f;
-   for (int r = 0; r < reps; r++) {
-      hipEventRecord(e0, c->stream);
+   auto triad = [&] {
       amgk::stream_triad(c->stream, a, b, d, 3.0, n);
-      hipEventRecord(e1, c->stream);
-      hipEventSynchronize(e1);
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, e0, e1);
+      return AMG_OK;
+   };
+   triad(); // warm
+   double best = 1e30, ms = 0.0;
+   int st = AMG_OK;
+   for (int r = 0; r < reps && st == AMG_OK; r++) {
+      st = amg_timed_reps(c->stream, 1, triad, &ms);
       best = std::min(best, ms);
    }
    const hipError_t err = hipGetLastError();
-   hipEventDestroy(e0);
-   hipEventDestroy(e1);
    hipFree(a);
    hipFree(b);
    hipFree(d);
+   AMG_TRY(st);
    AMG_HIP(err);
    *gbs = 24.0 * (double)n / (best * 1e-3) / 1e9;
    return AMG_OK;
@@ -1551,19 +1538,12 @@ extern "C" int amg_dev_tune_spmv(amg_ctx *c, const amg_mat *A, const amg_vec *x,
 {
    AMG_ARG(c && A && x && y && ms && reps >= 1, "amg_dev_tune_spmv: bad argument");
    AMG_ARG(variant >= 0 && variant < amgk::num_tune_variants(), "amg_dev_tune_spmv: variant");
-   hipEvent_t a, b;
-   AMG_HIP(hipEventCreate(&a));
-   AMG_HIP(hipEventCreate(&b));
-   AMG_HIP(hipEventRecord(a, c->stream));
-   for (int r = 0; r < reps; r++) amgk::launch_tune_variant(c->stream, variant, A, x->d, y->d);
-   AMG_HIP(hipEventRecord(b, c->stream));
-   AMG_HIP(hipEventSynchronize(b));
+   auto launch = [&] {
+      amgk::launch_tune_variant(c->stream, variant, A, x->d, y->d);
+      return AMG_OK;
+   };
+   AMG_TRY(amg_timed_reps(c->stream, reps, launch, ms));
    AMG_HIP(hipGetLastError());
-   float t = 0.f;
-   AMG_HIP(hipEventElapsedTime(&t, a, b));
-   hipEventDestroy(a);
-   hipEventDestroy(b);
-   *ms = (double)t / reps;
    return AMG_OK;
 }
 #endif // AMG_DEV_TUNE

@@ -521,28 +521,6 @@ int halo_end(amg_dist_hier *D, DistMat &M)
    return AMG_OK;
 }
 
-struct DProf {
-   amg_dist_hier *D;
-   int cat;
-   bool on;
-   hipEvent_t a = nullptr, b = nullptr;
-   DProf(amg_dist_hier *D_, int cat_, bool en) : D(D_), cat(cat_), on(en && D_->o.profile)
-   {
-      if (on) {
-         hipEventCreate(&a);
-         hipEventCreate(&b);
-         hipEventRecord(a, D->ctx->stream);
-      }
-   }
-   ~DProf()
-   {
-      if (on) {
-         hipEventRecord(b, D->ctx->stream);
-         D->pend[cat].push_back({a, b});
-      }
-   }
-};
-
 // interior rows first (overlapping the exchange), boundary rows after it
 template <class F>
 int split_launch(amg_dist_hier *D, DistMat &M, double *x, F launch)
@@ -903,11 +881,6 @@ extern "C" int amg_dist_hier_free(amg_dist_hier *D)
    if (D->coarse) amg_hier_free(D->coarse);
    for (auto *m : D->coarse_mats) amg_mat_free(m);
    for (void *p : D->allocs) hipFree(p);
-   for (int k = 0; k < 5; k++)
-      for (auto &e : D->pend[k]) {
-         hipEventDestroy(e.first);
-         hipEventDestroy(e.second);
-      }
    if (D->ev_pack) hipEventDestroy(D->ev_pack);
    if (D->ev_comm) hipEventDestroy(D->ev_comm);
    delete D;
@@ -975,7 +948,7 @@ int d_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_re
          std::swap(v.u, v.u_alt);
          D->pre_ready = false;
       } else {
-         DProf pr(D, 1, l == 0);
+         AmgProfLog::Scope pr(D->prof, 1, D->ctx->stream, D->o.profile && l == 0);
          double *x = v.u, *out = v.u_alt;
          AMG_TRY(split_launch(D, v.A, x, [&](int rb, int re, int) {
             amgk::jacobi_sweep(s, v.A.A, f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, out, rb, re);
@@ -1005,11 +978,11 @@ int d_vcycle(amg_dist_hier *D, bool precond)
       v.zero_flag = (l == 0 && !precond) ? 0 : 1;
       AMG_TRY(d_smooth(D, l, fl, D->o.num_pre_smooth_sweeps, l == 0 && d_reuse(D)));
       {
-         DProf pr(D, 0, l == 0);
+         AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile && l == 0);
          AMG_TRY(d_spgemv(D, v.A, v.u, fl, res_mode, v.r_fine, nullptr));
       }
       {
-         DProf pr(D, 2, l == 0);
+         AmgProfLog::Scope pr(D->prof, 2, D->ctx->stream, D->o.profile && l == 0);
          double *dst = (l + 1 < Ld) ? D->lv[l + 1].f : D->gath_buf + (size_t)D->gath_blk * c->xport->nranks;
          AMG_TRY(d_spgemv(D, v.R, v.r_fine, nullptr, mv_mode, dst, nullptr));
          if (l + 1 == Ld) {
@@ -1034,7 +1007,7 @@ int d_vcycle(amg_dist_hier *D, bool precond)
       DLevel &v = D->lv[l];
       v.zero_flag = 0;
       {
-         DProf pr(D, 3, l == 0);
+         AmgProfLog::Scope pr(D->prof, 3, D->ctx->stream, D->o.profile && l == 0);
          double *xc = (l + 1 < Ld) ? D->lv[l + 1].u : const_cast<double *>(u_rep);
          AMG_TRY(d_spgemv(D, v.P, xc, v.u, pro_mode, v.u, nullptr));
       }
@@ -1054,7 +1027,7 @@ int d_outer_residual(amg_dist_hier *D, int slot)
    const int np = nparts(v.A);
    AMG_TRY(amg_ctx_partials(c, np + 1, &p));
    {
-      DProf pr(D, 4, true);
+      AmgProfLog::Scope pr(D->prof, 4, D->ctx->stream, D->o.profile);
       if (d_reuse(D) && D->L > 1) {
          const bool l1 = D->o.smoother == AMG_L1_JACOBI;
          // reuse_outer_residual 2: the MULT cycle never reads r0 outside
@@ -1199,25 +1172,7 @@ extern "C" int amg_dist_profile_read(amg_dist_hier *D, double *ms, long long *la
 {
    AMG_ARG(D, "amg_dist_profile_read: null hierarchy");
    AMG_HIP(hipStreamSynchronize(D->ctx->stream));
-   for (int k = 0; k < 5; k++) {
-      for (auto &e : D->pend[k]) {
-         float t = 0.f;
-         hipEventSynchronize(e.second);
-         if (hipEventElapsedTime(&t, e.first, e.second) == hipSuccess) {
-            D->prof_ms[k] += t;
-            D->prof_n[k]++;
-         }
-         hipEventDestroy(e.first);
-         hipEventDestroy(e.second);
-      }
-      D->pend[k].clear();
-      if (ms) ms[k] = D->prof_ms[k];
-      if (launches) launches[k] = D->prof_n[k];
-      if (reset) {
-         D->prof_ms[k] = 0;
-         D->prof_n[k] = 0;
-      }
-   }
+   D->prof.read(ms, launches, reset);
    return AMG_OK;
 }
 
@@ -1227,18 +1182,6 @@ extern "C" int amg_dist_fine_spmv(amg_dist_hier *D, int reps, double *ms)
    if (D->slab) return slab_fine_spmv(D, reps, ms);
    amg_ctx *c = D->ctx;
    DLevel &v = D->lv[0];
-   hipEvent_t a, b;
-   AMG_HIP(hipEventCreate(&a));
-   AMG_HIP(hipEventCreate(&b));
    const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   AMG_HIP(hipEventRecord(a, c->stream));
-   for (int r = 0; r < reps; r++) AMG_TRY(d_spgemv(D, v.A, v.u, nullptr, mv, v.r_fine, nullptr));
-   AMG_HIP(hipEventRecord(b, c->stream));
-   AMG_HIP(hipEventSynchronize(b));
-   float t = 0.f;
-   AMG_HIP(hipEventElapsedTime(&t, a, b));
-   hipEventDestroy(a);
-   hipEventDestroy(b);
-   *ms = (double)t / reps;
-   return AMG_OK;
+   return amg_timed_reps(c->stream, reps, [&] { return d_spgemv(D, v.A, v.u, nullptr, mv, v.r_fine, nullptr); }, ms);
 }

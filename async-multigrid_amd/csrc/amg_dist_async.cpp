@@ -389,9 +389,9 @@ int level_correction(amg_dist_hier *D, int k, int j = -1)
    // can (no acceleration step between them)
    const bool fuse_corr = k > 0 && o.accel_type == AMG_NO_ACCEL && fused_xfp0(D);
    // (the fused prolongation + atomic correction: its whole launch is the window)
-   if (j >= 0 && fuse_corr && D->corr.record_start(k, j, s))
+   if (j >= 0 && fuse_corr && D->race.corr.record_start(k, j, s))
       return amg_set_error(AMG_ERR_HIP, "level %d: correction event", k);
-   unsigned long long *stp = j >= 0 ? D->corr.stamp(k, j) : nullptr;
+   unsigned long long *stp = j >= 0 ? D->race.corr.stamp(k, j) : nullptr;
    for (int l = k - 1; l >= 0; l--)
       AMG_TRY(prolong_to(D, a, l, a.e[l + 1], a.e[l], (l == 0 && fuse_corr) ? 1 : 0, D->lv[0].u, a.u_priv,
                          (l == 0 && fuse_corr) ? stp : nullptr));
@@ -408,10 +408,10 @@ int level_correction(amg_dist_hier *D, int k, int j = -1)
          amgk::vcopy(s, a.e[0], a.d_acc, 0, n0);
    }
    // correction into the shared slab; u_priv = the value each row saw
-   if (j >= 0 && !fuse_corr && D->corr.record_start(k, j, s))
+   if (j >= 0 && !fuse_corr && D->race.corr.record_start(k, j, s))
       return amg_set_error(AMG_ERR_HIP, "level %d: correction event", k);
    if (!fuse_corr) amgk::atomic_correct(s, D->lv[0].u, a.e[0], a.u_priv, n0, stp);
-   if (j >= 0 && D->corr.record(k, j, s)) return amg_set_error(AMG_ERR_HIP, "level %d: correction event", k);
+   if (j >= 0 && D->race.corr.record(k, j, s)) return amg_set_error(AMG_ERR_HIP, "level %d: correction event", k);
    // private residual r_k = f - A u_k  (SMEM_Residual on u_k)
    AMG_TRY(a_spgemv(D, a, D->lv[0].A, a.u_priv, nullptr, amgk::gemv_mode(1.0, 0.0), a.y));
    amgk::vsub(s, D->lv[0].f, a.y, a.r[0], 0, n0);
@@ -665,7 +665,7 @@ extern "C" int amg_dist_async_solve(amg_dist_hier *D, const double *f_local, int
    AMG_ARG(D->L >= 2, "amg_dist_async_solve: needs at least two levels");
    const int sched = D->o.async_schedule;
    AMG_ARG(sched >= AMG_SCHED_FREE && sched <= AMG_SCHED_TIMED, "amg_dist_async_solve: async_schedule %d", sched);
-   AMG_ARG(sched != AMG_SCHED_TIMED || ((int)D->async_dur.size() >= D->L && (int)D->async_t.size() >= D->L),
+   AMG_ARG(sched != AMG_SCHED_TIMED || D->race.timed_ready(D->L),
            "amg_dist_async_solve: AMG_SCHED_TIMED needs amg_dist_hier_set_async_durations / _times");
    amg_ctx *c = D->ctx;
    AMG_TRY(setup_async(D));
@@ -685,17 +685,17 @@ extern "C" int amg_dist_async_solve(amg_dist_hier *D, const double *f_local, int
       std::vector<long long> koff(D->L, 0);
       for (int k = 1; k < active; k++)
          if (D->o.accel_type == AMG_NO_ACCEL && fused_xfp0(D)) koff[k] = D->lv[0].sg.off();
-      if (D->corr.stamps_begin(c->stream, D->L, std::max(1, D->o.num_cycles), n0, koff))
+      if (D->race.corr.stamps_begin(c->stream, D->L, std::max(1, D->o.num_cycles), n0, koff))
          return amg_set_error(AMG_ERR_OOM, "amg_dist_async_solve: update-window stamps");
    }
-   hipEvent_t ready, t_start;
-   std::vector<hipEvent_t> t_end(active);
-   AMG_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-   AMG_HIP(hipEventCreate(&t_start));
-   for (auto &e : t_end) AMG_HIP(hipEventCreate(&e));
+   AmgEvent ready, t_start;
+   std::vector<AmgEvent> t_end(active);
+   AMG_TRY(ready.create(hipEventDisableTiming));
+   AMG_TRY(t_start.create());
+   for (auto &e : t_end) AMG_TRY(e.create());
    AMG_HIP(hipEventRecord(ready, c->stream));
    AMG_HIP(hipEventRecord(t_start, c->stream));
-   D->corr.reset(D->L);
+   D->race.corr.reset(D->L);
    for (int k = 0; k < active; k++) {
       AMG_HIP(hipStreamWaitEvent(D->al[k].s, ready, 0));
       // level_vector[k].r[0] = vector.r[0] (SMEM_Async_AMG.cpp:10-15)
@@ -731,27 +731,12 @@ extern "C" int amg_dist_async_solve(amg_dist_hier *D, const double *f_local, int
          });
       for (auto &t : th) t.join();
    } else {
-      // the oracle's or_set_async_schedule order: 1 / 2 level after level, 3
-      // cycle-major round robin, 4 timed (end times (j+1) dur[k], ties to the
-      // finer level); every rank issues the same sequence
-      std::vector<int> done_k(active, 0);
-      for (int q = 0; q < active * N && st[0] == AMG_OK; q++) {
-         int k;
-         if (sched == AMG_SCHED_ROUND_ROBIN) {
-            k = q % active;
-         } else if (sched == AMG_SCHED_TIMED) {
-            k = -1;
-            double tb = 0.0;
-            for (int j = 0; j < active; j++) {
-               if (done_k[j] >= N) continue;
-               const double t = amg_timed_end(D->async_t[j], D->async_dur[j], done_k[j]);
-               if (k < 0 || t < tb) k = j, tb = t;
-            }
-         } else {
-            k = sched == AMG_SCHED_FINEST_FIRST ? q / N : active - 1 - q / N;
-         }
+      // the oracle's or_set_async_schedule order (AmgAsyncTurns, converge
+      // LOCAL); every rank issues the same sequence
+      AmgAsyncTurns turns(sched, 0, active, active, N, false, D->race);
+      int k;
+      for (bool last; st[0] == AMG_OK && turns.next(&k, &last);) {
          st[0] = correct(k);
-         const bool last = ++done_k[k] == N;
          if (st[0] == AMG_OK && last && hipEventRecord(t_end[k], D->al[k].s) != hipSuccess)
             st[0] = amg_set_error(AMG_ERR_HIP, "level %d: hipEventRecord", k);
       }
@@ -760,17 +745,13 @@ extern "C" int amg_dist_async_solve(amg_dist_hier *D, const double *f_local, int
    }
    for (int k = 0; k < active; k++) {
       if (st[k] == AMG_OK && N <= 0) AMG_HIP(hipEventRecord(t_end[k], D->al[k].s));
-      hipEvent_t done;
-      AMG_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+      AmgEvent done;
+      AMG_TRY(done.create(hipEventDisableTiming));
       AMG_HIP(hipEventRecord(done, D->al[k].s)); // everything level k issued (drains included)
       AMG_HIP(hipStreamWaitEvent(c->stream, done, 0));
-      AMG_HIP(hipEventDestroy(done));
    }
-   AMG_HIP(hipEventDestroy(ready));
    for (int k = 0; k < active; k++)
       if (st[k] != AMG_OK) {
-         for (auto &e : t_end) hipEventDestroy(e);
-         hipEventDestroy(t_start);
          for (auto &a : D->al) hipStreamSynchronize(a.s);
          if (sched == AMG_SCHED_FREE) return amg_set_error(st[k], "level %d: %s", k, msg[k].c_str());
          return st[k];
@@ -785,52 +766,35 @@ extern "C" int amg_dist_async_solve(amg_dist_hier *D, const double *f_local, int
    if (sched == AMG_SCHED_FREE) {
       std::vector<int> cnt(D->L, 0);
       for (int k = 0; k < active; k++) cnt[k] = N;
-      if (D->corr.collect(t_start, cnt)) return amg_set_error(AMG_ERR_HIP, "amg_dist_async_solve: correction times");
-      if (D->corr.stamps_collect(cnt, c->wall_khz))
+      if (D->race.corr.collect(t_start, cnt)) return amg_set_error(AMG_ERR_HIP, "amg_dist_async_solve: correction times");
+      if (D->race.corr.stamps_collect(cnt, c->wall_khz))
          return amg_set_error(AMG_ERR_HIP, "amg_dist_async_solve: update-window stamps");
    }
-   D->level_ms.assign(D->L, 0.0);
+   D->race.level_ms.assign(D->L, 0.0);
    for (int k = 0; k < active; k++) {
       float ms = 0.f;
       AMG_HIP(hipEventElapsedTime(&ms, t_start, t_end[k]));
-      D->level_ms[k] = ms;
-      AMG_HIP(hipEventDestroy(t_end[k]));
+      D->race.level_ms[k] = ms;
    }
-   AMG_HIP(hipEventDestroy(t_start));
    return AMG_OK;
 }
 
 extern "C" int amg_dist_hier_set_async_durations(amg_dist_hier *D, const double *ms, int n)
 {
    AMG_ARG(D && ms && n >= D->L, "amg_dist_hier_set_async_durations: need %d levels", D ? D->L : 0);
-   for (int k = 0; k < D->L; k++)
-      AMG_ARG(ms[k] > 0.0, "amg_dist_hier_set_async_durations: level %d: %g", k, ms[k]);
-   D->async_dur.assign(ms, ms + D->L);
-   D->async_t.assign(D->L, {});
-   return AMG_OK;
+   return D->race.set_durations("amg_dist_hier_set_async_durations", ms, D->L);
 }
 
 extern "C" int amg_dist_hier_set_async_times(amg_dist_hier *D, const double *t, const int *n, int nlev)
 {
    AMG_ARG(D && t && n && nlev >= D->L, "amg_dist_hier_set_async_times: need %d levels", D ? D->L : 0);
-   D->async_t.assign(D->L, {});
-   D->async_dur.assign(D->L, 1.0);
-   for (int k = 0, off = 0; k < D->L; off += n[k], k++) {
-      AMG_ARG(n[k] >= 0, "amg_dist_hier_set_async_times: level %d: %d entries", k, n[k]);
-      D->async_t[k].assign(t + off, t + off + n[k]);
-   }
-   return AMG_OK;
+   return D->race.set_times("amg_dist_hier_set_async_times", t, n, D->L);
 }
 
 extern "C" int amg_dist_async_update_windows(const amg_dist_hier *D, int level, double *ms, int cap, int *count)
 {
    AMG_ARG(D && count && level >= 0 && level < D->L, "amg_dist_async_update_windows: bad argument");
-   const bool start = cap < 0;
-   if (start) cap = -cap;
-   const auto &vv = start ? D->corr.w0 : D->corr.w1;
-   const auto &v = level < (int)vv.size() ? vv[level] : std::vector<double>();
-   *count = (int)v.size();
-   for (int j = 0; j < (int)v.size() && j < cap && ms; j++) ms[j] = v[j];
+   D->race.update_windows(level, ms, cap, count);
    return AMG_OK;
 }
 
@@ -839,28 +803,21 @@ extern "C" int amg_dist_async_update_rows(const amg_dist_hier *D, int level, int
 {
    AMG_ARG(D && count && level >= 0 && level < D->L && corr >= 0,
            "amg_dist_async_update_rows: bad argument");
-   *count = D->corr.rows_of(level, corr, ms, cap < 0 ? -cap : cap, cap < 0);
+   D->race.update_rows(level, corr, ms, cap, count);
    return AMG_OK;
 }
 
 extern "C" int amg_dist_async_correction_ms(const amg_dist_hier *D, int level, double *ms, int cap, int *count)
 {
    AMG_ARG(D && count && level >= 0 && level < D->L, "amg_dist_async_correction_ms: bad argument");
-   const bool start = cap < 0; // cap < 0: the update windows' start times, -cap entries
-   if (start) cap = -cap;
-   const auto &vv = start ? D->corr.ms0 : D->corr.ms;
-   const auto &v = level < (int)vv.size() ? vv[level] : std::vector<double>();
-   *count = (int)v.size();
-   for (int j = 0; j < (int)v.size() && j < cap && ms; j++) ms[j] = v[j];
+   D->race.correction_ms(level, ms, cap, count);
    return AMG_OK;
 }
 
 extern "C" int amg_dist_async_level_ms(const amg_dist_hier *D, double *ms)
 {
    AMG_ARG(D && ms, "amg_dist_async_level_ms: null argument");
-   AMG_ARG(!D->level_ms.empty(), "amg_dist_async_level_ms: no asynchronous solve yet");
-   for (int k = 0; k < D->L; k++) ms[k] = D->level_ms[k];
-   return AMG_OK;
+   return D->race.copy_level_ms("amg_dist_async_level_ms", ms, D->L);
 }
 
 // ---------------------------------------------------------------------------
@@ -1133,20 +1090,19 @@ int async_jacobi_run(amg_dist_hier *D, const double *f_local, int sweeps, int l1
    amgk::vset(s, eext, 0.0, 0, v.cap);
    amgk::vset(s, gext, 0.0, 0, v.cap);
    const amgk::Gemv upd = amgk::gemv_mode(-1.0, 1.0); // r = r - A z
-   hipEvent_t packed[AJ_NBUF], sent[AJ_NBUF], arrived[AJ_NBUF];
-   for (int q = 0; q < AJ_NBUF; q++) {
-      hipEventCreateWithFlags(&packed[q], hipEventDisableTiming);
-      hipEventCreateWithFlags(&sent[q], hipEventDisableTiming);
-      hipEventCreateWithFlags(&arrived[q], hipEventDisableTiming);
-   }
+   AmgEvent packed[AJ_NBUF], sent[AJ_NBUF], arrived[AJ_NBUF];
+   for (int q = 0; q < AJ_NBUF; q++)
+      for (AmgEvent *e : {&packed[q], &sent[q], &arrived[q]})
+         if ((st = e->create(hipEventDisableTiming)) != AMG_OK) return fail(st);
    // the overlap record: per sweep the exchange window on the comm stream and
    // the interior product's window on the compute stream (timing events)
-   std::vector<hipEvent_t> tev((size_t)sweeps * 4, nullptr);
-   for (auto &e : tev) hipEventCreate(&e);
-   auto tx0 = [&](int k) { return tev[(size_t)k * 4]; };
-   auto tx1 = [&](int k) { return tev[(size_t)k * 4 + 1]; };
-   auto ti0 = [&](int k) { return tev[(size_t)k * 4 + 2]; };
-   auto ti1 = [&](int k) { return tev[(size_t)k * 4 + 3]; };
+   std::vector<AmgEvent> tev((size_t)sweeps * 4);
+   for (auto &e : tev)
+      if ((st = e.create()) != AMG_OK) return fail(st);
+   auto tx0 = [&](int k) { return tev[(size_t)k * 4].e; };
+   auto tx1 = [&](int k) { return tev[(size_t)k * 4 + 1].e; };
+   auto ti0 = [&](int k) { return tev[(size_t)k * 4 + 2].e; };
+   auto ti1 = [&](int k) { return tev[(size_t)k * 4 + 3].e; };
    // the deltas through device-resident channels (amg_link.cpp) where the
    // ranks share a node: a send is a copy kernel on the comm stream straight
    // into the neighbour's slot (overlapping the interior product on the
@@ -1357,15 +1313,7 @@ int async_jacobi_run(amg_dist_hier *D, const double *f_local, int sweeps, int l1
    };
    st = sweep_all();
    if (st != AMG_OK && use_links) link_abort(D->ajac_links);
-   for (int q = 0; q < AJ_NBUF; q++) {
-      hipEventDestroy(packed[q]);
-      hipEventDestroy(sent[q]);
-      hipEventDestroy(arrived[q]);
-   }
-   if (st != AMG_OK) {
-      for (auto e : tev) hipEventDestroy(e);
-      return fail(st);
-   }
+   if (st != AMG_OK) return fail(st);
    // the overlap record: the fraction of each sweep's exchange window that the
    // interior product covers, the windows' lengths
    {
@@ -1399,7 +1347,6 @@ int async_jacobi_run(amg_dist_hier *D, const double *f_local, int sweeps, int l1
       D->ajac_stats[4] = use_links ? (double)late : -1.0;
       D->ajac_stats[7] = use_links ? 1.0 : 0.0;
    }
-   for (auto e : tev) hipEventDestroy(e);
    // every delta applied once <=> the incrementally kept r equals f - A x (to
    // rounding): its global norm, beside the true residual's below
    {

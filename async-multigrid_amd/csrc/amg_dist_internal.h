@@ -9,7 +9,7 @@
 #include <map>
 #include <vector>
 
-#include "amg_internal.h"
+#include "amg_async.h"
 
 struct amg_transport {
    int nranks = 1, rank = 0;
@@ -218,8 +218,7 @@ struct amg_dist_hier {
    bool pre_ready = false, have_state = false;
    hipEvent_t ev_pack = nullptr, ev_comm = nullptr;
    std::vector<void *> allocs;
-   // profiling: [0] fine residual, [1] fine smoother, [2] R0, [3] P0, [4] outer residual
-   std::vector<std::pair<hipEvent_t, hipEvent_t>> pend[5];
+   AmgProfLog prof; // recorded on ctx->stream
    // asynchronous additive cycle (built on first use): per-level state and
    // the per-level device-resident channels between ranks
    std::vector<amgd::AsyncLevel> al;
@@ -242,12 +241,7 @@ struct amg_dist_hier {
    double *x_acc = nullptr, *d_acc = nullptr;
    amgd::AccelState acc;
    GridState grid;
-   std::vector<double> level_ms; // amg_dist_async_level_ms
-   std::vector<double> async_dur; // AMG_SCHED_TIMED: per-level correction time
-   std::vector<std::vector<double>> async_t; // AMG_SCHED_TIMED: recorded end times (replay)
-   AmgCorrTimes corr;             // per-correction end times of the last free race
-   double prof_ms[5] = {0, 0, 0, 0, 0};
-   long long prof_n[5] = {0, 0, 0, 0, 0};
+   AmgRaceRecord race; // AMG_SCHED_TIMED level speeds and the last asynchronous solve's records
 };
 
 namespace amgd {

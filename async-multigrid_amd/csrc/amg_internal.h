@@ -59,211 +59,6 @@ constexpr int AMG_PP_LDS = 32 * 1024;
 constexpr int AMG_PP_LONG_MIN_ROWS = 1 << 22;
 inline int amg_pp_stride(int maxrow) { return 1 + 2 * (maxrow <= 8 ? 8 : AMG_PP_MAXROW); }
 
-// AMG_SCHED_TIMED: the end time of a level's correction j (0-based) -- its
-// recorded end times t (the replay of a measured race; past the table the
-// last interval repeats) or, without a table, (j + 1) dur.  The oracle's
-// timed_end (or_set_async_durations / or_set_async_times), the same doubles.
-inline double amg_timed_end(const std::vector<double> &t, double dur, int j)
-{
-   const int n = (int)t.size();
-   if (n == 0) return (double)(j + 1) * dur;
-   if (j < n) return t[j];
-   const double dt = n > 1 ? t[n - 1] - t[n - 2] : t[0];
-   return t[n - 1] + (double)(j - n + 1) * dt;
-}
-
-namespace amgk {
-void stamp_init(hipStream_t s, unsigned long long *stamps, int n);
-}
-
-// per-correction end events of a free race (one pool per level, grown on use)
-// (the update point of correction j: its start event `record_start`, before
-// the kernel that adds it into the shared iterate, and its end event `record`,
-// after it -- a window in which other levels' updates may interleave row by row)
-struct AmgCorrTimes {
-   std::vector<std::vector<hipEvent_t>> ev, ev0; // [level][correction]: update end / start
-   std::vector<std::vector<double>> ms, ms0;     // [level][correction], after the solve
-   static int rec(std::vector<hipEvent_t> &v, int j, hipStream_t s)
-   {
-      while ((int)v.size() <= j) {
-         hipEvent_t e;
-         if (hipEventCreate(&e) != hipSuccess) return -1;
-         v.push_back(e);
-      }
-      return hipEventRecord(v[j], s) == hipSuccess ? 0 : -1;
-   }
-   int record(int k, int j, hipStream_t s) { return rec(ev[k], j, s); }
-   int record_start(int k, int j, hipStream_t s) { return rec(ev0[k], j, s); }
-   void reset(int L)
-   {
-      ev.resize(L);
-      ev0.resize(L);
-      ms.assign(L, {});
-      ms0.assign(L, {});
-   }
-   // elapsed ms of the first cnt[k] events of every level from t0
-   int collect(hipEvent_t t0, const std::vector<int> &cnt)
-   {
-      ms.assign(ev.size(), {});
-      ms0.assign(ev.size(), {});
-      for (size_t k = 0; k < ev.size() && k < cnt.size(); k++)
-         for (int j = 0; j < cnt[k] && j < (int)ev[k].size(); j++) {
-            float m = 0.f;
-            if (hipEventElapsedTime(&m, t0, ev[k][j]) != hipSuccess) return -1;
-            ms[k].push_back(m);
-            if (j < (int)ev0[k].size()) {
-               if (hipEventElapsedTime(&m, t0, ev0[k][j]) != hipSuccess) return -1;
-               ms0[k].push_back(m);
-            }
-         }
-      return 0;
-   }
-   // device execution windows of the update kernels (stamp_begin / stamp_end
-   // in the kernel that adds correction j of level k into the shared vector):
-   // [k][j] start / end in ms of the device wall clock (an arbitrary origin
-   // common to every stream and process on the device); NaN: not stamped.
-   // Record of correction (k, j): 4 words -- window start, window end, the
-   // device address of its per-row stamp array (0: none), unused.
-   unsigned long long *d_st = nullptr;
-   int st_cap = 0, st_L = 0;
-   std::vector<std::vector<double>> w0, w1;
-   // per-row update times (stamp_row: the low 32 bits of the device wall clock
-   // at which row i's add + read of the shared vector completed) of the first
-   // rows_j corrections of every level; rows_ms[k][j]: nrow times in ms, on the
-   // window clock (empty: not recorded)
-   unsigned *d_rows = nullptr;
-   double *d_vals = nullptr; // per row: the value each add replaced and the value it left
-   size_t rows_alloc = 0;
-   int nrow = 0, rows_j = 0;
-   std::vector<std::vector<std::vector<double>>> rows_ms, rows_vals;
-   std::vector<unsigned long long> h_init;
-   // row stamps are taken while nrow * L * rows_j * 20 B stays within this
-   static constexpr size_t kRowBudget = (size_t)512 << 20;
-   // koff[k]: the index of owned row 0 in the vector the update kernel of
-   // level k indexes (a slab level-0 vector with its ghost planes in front)
-   int stamps_begin(hipStream_t s, int L, int cap, int n_rows = 0, const std::vector<long long> &koff = {})
-   {
-      if (!d_st || L * cap > st_L * st_cap) {
-         if (d_st) hipFree(d_st);
-         d_st = nullptr;
-         if (hipMalloc((void **)&d_st, (size_t)4 * L * cap * sizeof(unsigned long long)) != hipSuccess) return -1;
-      }
-      st_L = L;
-      st_cap = cap;
-      nrow = n_rows > 0 ? n_rows : 0;
-      rows_j = nrow > 0 ? (int)std::min<size_t>(cap, kRowBudget / ((size_t)nrow * L * 20)) : 0;
-      const size_t need = (size_t)nrow * L * rows_j;
-      if (need > rows_alloc) {
-         if (d_rows) hipFree(d_rows);
-         if (d_vals) hipFree(d_vals);
-         d_rows = nullptr;
-         d_vals = nullptr;
-         rows_alloc = 0;
-         if (hipMalloc((void **)&d_rows, need * sizeof(unsigned)) != hipSuccess ||
-             hipMalloc((void **)&d_vals, 2 * need * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            rows_j = 0;
-         } else {
-            rows_alloc = need;
-         }
-      }
-      if (rows_j == 0) {
-         // no row arrays: the records set on the device, in stream order (a
-         // pageable host copy per solve serialises the ranks sharing a GPU)
-         amgk::stamp_init(s, d_st, L * cap);
-         return 0;
-      }
-      h_init.assign((size_t)4 * L * cap, 0ull);
-      for (int k = 0; k < L; k++)
-         for (int j = 0; j < cap; j++) {
-            unsigned long long *w = &h_init[4 * ((size_t)k * cap + j)];
-            w[0] = ~0ull;
-            if (j < rows_j) {
-               const long long o = k < (int)koff.size() ? koff[k] : 0;
-               w[2] = (unsigned long long)(uintptr_t)(d_rows + ((size_t)k * rows_j + j) * nrow - o);
-               w[3] = (unsigned long long)(uintptr_t)(d_vals + 2 * (((size_t)k * rows_j + j) * nrow - o));
-            }
-         }
-      if (hipMemcpyAsync(d_st, h_init.data(), h_init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice,
-                         s) != hipSuccess)
-         return -1;
-      if (rows_j > 0 && hipMemsetAsync(d_rows, 0, need * sizeof(unsigned), s) != hipSuccess) return -1;
-      // NaN: a row whose update recorded no values (the no-return form)
-      if (rows_j > 0 && hipMemsetAsync(d_vals, 0xff, 2 * need * sizeof(double), s) != hipSuccess) return -1;
-      return 0;
-   }
-   unsigned long long *stamp(int k, int j) const
-   {
-      if (!(d_st && k >= 0 && k < st_L && j >= 0 && j < st_cap)) return nullptr;
-      unsigned long long *p = d_st + 4 * ((size_t)k * st_cap + j);
-      // low bit: the record carries row arrays (stamp_rows reads them only then)
-      return (j < rows_j && nrow > 0) ? reinterpret_cast<unsigned long long *>(reinterpret_cast<uintptr_t>(p) | 1)
-                                      : p;
-   }
-   // after the solve (the stream has finished): windows of the first cnt[k]
-   // corrections of every level, and their row times where recorded
-   int stamps_collect(const std::vector<int> &cnt, int wall_khz)
-   {
-      w0.assign(st_L, {});
-      w1.assign(st_L, {});
-      rows_ms.assign(st_L, {});
-      rows_vals.assign(st_L, {});
-      if (!d_st) return 0;
-      std::vector<unsigned long long> h((size_t)4 * st_L * st_cap);
-      if (hipMemcpy(h.data(), d_st, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
-         return -1;
-      const double tpm = wall_khz > 0 ? (double)wall_khz : 1e5; // ticks per ms
-      // the host copy of a correction's row times only where rows were
-      // recorded (nrow is the level-0 row count: a per-solve zero-filled
-      // buffer of that size cost 12 % of config 3's asynchronous cycle)
-      std::vector<unsigned> hr;
-      if (rows_j > 0) hr.resize((size_t)nrow);
-      for (int k = 0; k < st_L && k < (int)cnt.size(); k++)
-         for (int j = 0; j < cnt[k] && j < st_cap; j++) {
-            const unsigned long long a = h[4 * ((size_t)k * st_cap + j)], b = h[4 * ((size_t)k * st_cap + j) + 1];
-            const bool ok = a != ~0ull && b != 0ull;
-            w0[k].push_back(ok ? (double)a / tpm : std::numeric_limits<double>::quiet_NaN());
-            w1[k].push_back(ok ? (double)b / tpm : std::numeric_limits<double>::quiet_NaN());
-            if (!ok || j >= rows_j || nrow == 0) continue;
-            if (hipMemcpy(hr.data(), d_rows + ((size_t)k * rows_j + j) * nrow, (size_t)nrow * sizeof(unsigned),
-                          hipMemcpyDeviceToHost) != hipSuccess)
-               return -1;
-            // unwrap the low 32 bits around the window start (|dt| < 21 s)
-            if ((int)rows_ms[k].size() != j) continue;
-            std::vector<double> t((size_t)nrow);
-            for (int i = 0; i < nrow; i++) {
-               const int d = (int)(hr[i] - (unsigned)a);
-               t[i] = ((double)a + (double)d) / tpm;
-            }
-            rows_ms[k].push_back(std::move(t));
-            std::vector<double> v((size_t)2 * nrow);
-            if (hipMemcpy(v.data(), d_vals + 2 * ((size_t)k * rows_j + j) * nrow, v.size() * sizeof(double),
-                          hipMemcpyDeviceToHost) != hipSuccess)
-               return -1;
-            rows_vals[k].push_back(std::move(v));
-         }
-      return 0;
-   }
-   // per-row times of correction j of level k: nrow values, or 0 if not
-   // recorded; vals: the 2 nrow (old, new) values instead
-   int rows_of(int k, int j, double *out, int cap, bool vals = false) const
-   {
-      const auto &src = vals ? rows_vals : rows_ms;
-      if (k < 0 || k >= (int)src.size() || j < 0 || j >= (int)src[k].size()) return 0;
-      const int n = std::min(cap, (int)src[k][j].size());
-      if (out) std::copy(src[k][j].begin(), src[k][j].begin() + n, out);
-      return n;
-   }
-   ~AmgCorrTimes()
-   {
-      for (auto *vv : {&ev, &ev0})
-         for (auto &v : *vv)
-            for (auto e : v) hipEventDestroy(e);
-      if (d_st) hipFree(d_st);
-      if (d_rows) hipFree(d_rows);
-      if (d_vals) hipFree(d_vals);
-   }
-};
 // anchored operators (interpolation, restriction): row 2t+1's anchor minus
 // row 2t's, + AMG_PP_DA0, must lie in [0, AMG_PP_NDA)
 constexpr int AMG_PP_NDA = 16;

@@ -238,28 +238,6 @@ int split_A(amg_dist_hier *D, const DistMat &M, double *x, F launch, long long *
    return AMG_OK;
 }
 
-struct SProf {
-   amg_dist_hier *D;
-   int cat;
-   bool on;
-   hipEvent_t a = nullptr, b = nullptr;
-   SProf(amg_dist_hier *D_, int cat_, bool en) : D(D_), cat(cat_), on(en && D_->o.profile)
-   {
-      if (on) {
-         hipEventCreate(&a);
-         hipEventCreate(&b);
-         hipEventRecord(a, D->ctx->stream);
-      }
-   }
-   ~SProf()
-   {
-      if (on) {
-         hipEventRecord(b, D->ctx->stream);
-         D->pend[cat].push_back({a, b});
-      }
-   }
-};
-
 bool s_reuse(const amg_dist_hier *D)
 {
    return D->o.reuse_outer_residual && D->o.num_pre_smooth_sweeps > 0 && !dist_mult_accel(D);
@@ -291,7 +269,7 @@ int s_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_re
          std::swap(v.u, v.u_alt);
          D->pre_ready = false;
       } else {
-         SProf pr(D, 1, l == 0);
+         AmgProfLog::Scope pr(D->prof, 1, D->ctx->stream, D->o.profile && l == 0);
          double *x = v.u, *out = v.u_alt;
          AMG_TRY(split_A(D, v.A, x, [&](long long rb, long long re, long long) {
             slab_jacobi(s, v.A, f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, out, rb, re);
@@ -463,7 +441,7 @@ int amgd::slab_vcycle(amg_dist_hier *D, bool precond)
          zg.err = c->d_err;
       }
       if (l == 0 && D->geo0) {
-         SProf pr(D, 0, true);
+         AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile);
          // the right-hand side's ghost planes: f's were exchanged at the solve's
          // start; the outer residual (preconditioner mode) changes every cycle
          if (precond) AMG_TRY(slab_xchg(c, s, fl, v.n, v.sg.P, D->rr_flo, D->rr_fhi));
@@ -473,12 +451,12 @@ int amgd::slab_vcycle(amg_dist_hier *D, bool precond)
          if (!to_rep) D->lv[l + 1].zero_done = zg.u != nullptr;
       } else {
          {
-            SProf pr(D, 0, l == 0);
+            AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile && l == 0);
             AMG_TRY(split_A(D, v.A, v.u, [&](long long rb, long long re, long long) {
                slab_spgemv(s, v.A, v.u, fl, res_mode, v.r_fine, rb, re, nullptr);
             }));
          }
-         SProf pr(D, 2, l == 0);
+         AmgProfLog::Scope pr(D->prof, 2, D->ctx->stream, D->o.profile && l == 0);
          AMG_TRY(slab_restrict(D, s, l, v.r_fine, dst, xchg, v.geo ? zg : amgk::ZeroGuess()));
          if (!to_rep) D->lv[l + 1].zero_done = v.geo && zg.u != nullptr;
       }
@@ -496,7 +474,7 @@ int amgd::slab_vcycle(amg_dist_hier *D, bool precond)
       DLevel &v = D->lv[l];
       v.zero_flag = 0;
       {
-         SProf pr(D, 3, l == 0);
+         AmgProfLog::Scope pr(D->prof, 3, D->ctx->stream, D->o.profile && l == 0);
          double *xc = (l + 1 < Ld) ? D->lv[l + 1].u : const_cast<double *>(u_rep);
          AMG_TRY(slab_prolong(D, s, l, xc, v.u, true, xchg));
       }
@@ -515,7 +493,7 @@ int amgd::slab_outer_residual(amg_dist_hier *D, int slot)
    double *p;
    AMG_TRY(amg_ctx_partials(c, (size_t)tiles(v.n) + 8, &p));
    {
-      SProf pr(D, 4, true);
+      AmgProfLog::Scope pr(D->prof, 4, D->ctx->stream, D->o.profile);
       if (s_reuse(D) && D->L > 1) {
          const bool l1 = D->o.smoother == AMG_L1_JACOBI;
          double *r0 = (D->o.reuse_outer_residual >= 2 && D->o.solver == AMG_MULT) ? nullptr : D->r0;
@@ -575,23 +553,13 @@ int amgd::slab_fine_spmv(amg_dist_hier *D, int reps, double *ms)
    amg_ctx *c = D->ctx;
    DLevel &v = D->lv[0];
    hipStream_t s = c->stream;
-   hipEvent_t a, b;
-   AMG_HIP(hipEventCreate(&a));
-   AMG_HIP(hipEventCreate(&b));
    const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   AMG_HIP(hipEventRecord(a, s));
-   for (int r = 0; r < reps; r++)
-      AMG_TRY(split_A(D, v.A, v.u, [&](long long rb, long long re, long long) {
+   auto spmv = [&] {
+      return split_A(D, v.A, v.u, [&](long long rb, long long re, long long) {
          slab_spgemv(s, v.A, v.u, nullptr, mv, v.r_fine, rb, re, nullptr);
-      }));
-   AMG_HIP(hipEventRecord(b, s));
-   AMG_HIP(hipEventSynchronize(b));
-   float t = 0.f;
-   AMG_HIP(hipEventElapsedTime(&t, a, b));
-   hipEventDestroy(a);
-   hipEventDestroy(b);
-   *ms = (double)t / reps;
-   return AMG_OK;
+      });
+   };
+   return amg_timed_reps(s, reps, spmv, ms);
 }
 
 // ---------------------------------------------------------------------------

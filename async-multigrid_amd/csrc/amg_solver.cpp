@@ -11,7 +11,7 @@
 #include <thread>
 #include <vector>
 
-#include "amg_internal.h"
+#include "amg_async.h"
 
 int amg_reduce_to_host(amg_ctx *c, const double *partials, int np, int do_sqrt, double *out);
 int amg_hybrid_jgs_dev(amg_ctx *c, hipStream_t s, const amg_mat *A, const double *f, double *u,
@@ -26,8 +26,7 @@ int amg_sym_jacobi_dev(hipStream_t s, const amg_mat *A, const double *f, double 
 namespace {
 
 enum ProfCat { PROF_FINE_SPMV = 0, PROF_FINE_SMOOTH = 1, PROF_RESTRICT0 = 2, PROF_PROLONG0 = 3,
-               PROF_OUTER = 4,
-               PROF_NCAT = 5 };
+               PROF_OUTER = 4 };
 
 struct Level {
    amg_mat *A = nullptr, *P = nullptr, *R = nullptr;
@@ -50,7 +49,7 @@ struct AddLevel {
    // asynchronous options: READ_RES private correction sum (level_vector[k].f[0]),
    // GLOBAL residual phase's fine smoothing correction and scratch (n0 each)
    double *f_acc = nullptr, *g_u = nullptr, *g_prev = nullptr, *g_y = nullptr, *g_r = nullptr;
-   hipEvent_t ev_a = nullptr, ev_b = nullptr; // level stream <-> update stream (SEMI_ASYNC)
+   AmgEvent ev_a, ev_b;                 // level stream <-> update stream (SEMI_ASYNC)
    double *xt = nullptr, *xy = nullptr;       // composed smoothed transfers' scratch (n0 each)
 };
 
@@ -106,27 +105,17 @@ struct amg_hier {
    // fuse_outer 3 without a stored u': u' of one z-slab (slab_planes + 2 planes)
    double *slab_scr = nullptr;
    long long slab_cap = 0;
-   // AMG_SCHED_TIMED: per-level correction time (amg_hier_set_async_durations)
-   // or recorded end times (amg_hier_set_async_times)
-   std::vector<double> async_dur;
-   std::vector<std::vector<double>> async_t;
-   // per-correction end times of the last free race (amg_async_correction_ms)
-   AmgCorrTimes corr;
+   // AMG_SCHED_TIMED level speeds and the last asynchronous solve's records
+   AmgRaceRecord race;
    // the correction whose update-window start a fused update kernel records
    // (mark_update_start; -1: none)
    int mark_k = -1, mark_j = 0;
    unsigned long long *mark_stamp = nullptr; // its execution-window stamp
-   // per level of the last amg_async_solve: ms from its start to the level's
-   // last correction (amg_async_level_ms)
-   std::vector<double> level_ms;
    // delay / fault injection: one generator per reference thread (srand(tid),
    // SMEM_Solve.cpp:113), reset by every solve
    std::vector<unsigned long long> delay_rng;
    std::vector<void *> allocs;
-   // profiling
-   std::vector<std::pair<hipEvent_t, hipEvent_t>> pend[PROF_NCAT];
-   double prof_ms[PROF_NCAT] = {0, 0, 0, 0, 0};
-   long long prof_n[PROF_NCAT] = {0, 0, 0, 0, 0};
+   AmgProfLog prof;
 };
 
 static int dalloc(amg_hier *H, size_t n, double **p)
@@ -153,61 +142,11 @@ static bool is_multadd(const amg_opts &o)
    return o.solver == AMG_MULTADD || o.solver == AMG_ASYNC_MULTADD;
 }
 
-// ---- profiling helpers -----------------------------------------------------
-struct ProfScope {
-   amg_hier *H;
-   int cat;
-   hipStream_t s;
-   hipEvent_t a = nullptr, b = nullptr;
-   bool on;
-   ProfScope(amg_hier *H_, int cat_, hipStream_t s_, bool enabled = true)
-      : H(H_), cat(cat_), s(s_), on(enabled && H_->o.profile)
-   {
-      if (on) {
-         hipEventCreate(&a);
-         hipEventCreate(&b);
-         hipEventRecord(a, s);
-      }
-   }
-   ~ProfScope()
-   {
-      if (on) {
-         hipEventRecord(b, s);
-         H->pend[cat].push_back({a, b});
-      }
-   }
-};
-
-static void prof_drain(amg_hier *H)
-{
-   for (int c = 0; c < PROF_NCAT; c++) {
-      for (auto &p : H->pend[c]) {
-         float ms = 0.f;
-         hipEventSynchronize(p.second);
-         if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
-            H->prof_ms[c] += ms;
-            H->prof_n[c] += 1;
-         }
-         hipEventDestroy(p.first);
-         hipEventDestroy(p.second);
-      }
-      H->pend[c].clear();
-   }
-}
-
 extern "C" int amg_hier_profile_read(amg_hier *H, double *ms, long long *launches, int reset)
 {
    AMG_ARG(H, "amg_hier_profile_read: null hierarchy");
    AMG_HIP(hipStreamSynchronize(H->ctx->stream));
-   prof_drain(H);
-   for (int c = 0; c < PROF_NCAT; c++) {
-      if (ms) ms[c] = H->prof_ms[c];
-      if (launches) launches[c] = H->prof_n[c];
-      if (reset) {
-         H->prof_ms[c] = 0;
-         H->prof_n[c] = 0;
-      }
-   }
+   H->prof.read(ms, launches, reset);
    return AMG_OK;
 }
 
@@ -520,12 +459,7 @@ extern "C" int amg_hier_free(amg_hier *H)
    std::lock_guard<std::recursive_mutex> td(amg_teardown_mutex());
    hipStreamSynchronize(H->ctx->stream);
    for (auto s : H->ctx->level_streams) hipStreamSynchronize(s);
-   prof_drain(H);
    graphs_reset(H);
-   for (auto &a : H->al) {
-      if (a.ev_a) hipEventDestroy(a.ev_a);
-      if (a.ev_b) hipEventDestroy(a.ev_b);
-   }
    for (void *p : H->allocs) hipFree(p);
    for (auto &l : H->lv) hipFree(l.d_blk);
    delete H;
@@ -587,7 +521,7 @@ static void smooth_one_level(amg_hier *H, hipStream_t s, int l, const double *f,
    if (o.smoother == AMG_HYBRID_JACOBI_GAUSS_SEIDEL ||
        o.smoother == AMG_L1_HYBRID_JACOBI_GAUSS_SEIDEL) {
       const double *ds = (o.smoother == AMG_L1_HYBRID_JACOBI_GAUSS_SEIDEL) ? v.l1 : v.adiag;
-      ProfScope ps(H, PROF_FINE_SMOOTH, s, prof);
+      AmgProfLog::Scope ps(H->prof, PROF_FINE_SMOOTH, s, H->o.profile && prof);
       amg_hybrid_jgs_dev(H->ctx, s, v.A, f, v.u, v.u_prev, v.n, v.d_blk, (int)v.blk.size() - 1, 0,
                          v.n, ds, 1.0, sweeps, zf, 0);
       return;
@@ -595,7 +529,7 @@ static void smooth_one_level(amg_hier *H, hipStream_t s, int l, const double *f,
    if (o.smoother == AMG_ASYNC_GAUSS_SEIDEL || o.smoother == AMG_SEMI_ASYNC_GAUSS_SEIDEL) {
       // SMEM_Async_Parfor_GaussSeidel / SMEM_SemiAsync_Parfor_GaussSeidel
       // (SMEM_Solve.cpp:342-347): in place, no zero-guess special case
-      ProfScope ps(H, PROF_FINE_SMOOTH, s, prof);
+      AmgProfLog::Scope ps(H->prof, PROF_FINE_SMOOTH, s, H->o.profile && prof);
       amgk::async_gs(s, v.A, f, v.u, v.d_blk, (int)v.blk.size() - 1, sweeps,
                      o.smoother == AMG_SEMI_ASYNC_GAUSS_SEIDEL, 0);
       return;
@@ -619,7 +553,7 @@ static void smooth_one_level(amg_hier *H, hipStream_t s, int l, const double *f,
                                     v.u, 0, v.n);
       } else {
          {
-            ProfScope ps(H, PROF_FINE_SMOOTH, s, prof);
+            AmgProfLog::Scope ps(H->prof, PROF_FINE_SMOOTH, s, H->o.profile && prof);
             amgk::jacobi_sweep(s, v.A, f, v.u, l1 ? v.l1 : nullptr, o.smooth_weight, v.u_alt, 0, v.n);
          }
          std::swap(v.u, v.u_alt);
@@ -632,7 +566,7 @@ static void smooth_one_level(amg_hier *H, hipStream_t s, int l, const double *f,
 static void mark_update_start(amg_hier *H, hipStream_t s)
 {
    if (H->mark_k < 0) return;
-   H->corr.record_start(H->mark_k, H->mark_j, s);
+   H->race.corr.record_start(H->mark_k, H->mark_j, s);
    H->mark_k = -1;
 }
 
@@ -731,17 +665,17 @@ static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = f
       }
       if (l == 0 && H->geo0) {
          // level-0 residual and restriction in one pass (no r_fine vector)
-         ProfScope ps(H, PROF_FINE_SPMV, s);
+         AmgProfLog::Scope ps(H->prof, PROF_FINE_SPMV, s, H->o.profile);
          amgk::mz_residual_restrict(s, v.A, f_fine, v.u, H->gl[0], H->d_geo_w[0], nx.f, 0, -1, 0, 0, zg);
          nx.zero_done = zg.u != nullptr;
          continue;
       }
       {
-         ProfScope ps(H, PROF_FINE_SPMV, s, l == 0);
+         AmgProfLog::Scope ps(H->prof, PROF_FINE_SPMV, s, H->o.profile && l == 0);
          amgk::spgemv(s, v.A, v.u, f_fine, res_mode, v.r_fine, 0, v.n, nullptr);
       }
       {
-         ProfScope ps(H, PROF_RESTRICT0, s, l == 0);
+         AmgProfLog::Scope ps(H->prof, PROF_RESTRICT0, s, H->o.profile && l == 0);
          if (H->geo[l]) {
             amgk::geo_restrict(s, H->gl[l], H->d_geo_w[l], v.r_fine, nx.f, 0, -1, 0, 0, zg);
             nx.zero_done = zg.u != nullptr;
@@ -762,7 +696,7 @@ static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = f
          // u += P e fused into the first post sweep (the corrected u is never
          // stored; the sweep's output is the same bits)
          {
-            ProfScope ps(H, PROF_FINE_SMOOTH, s, l == 0);
+            AmgProfLog::Scope ps(H->prof, PROF_FINE_SMOOTH, s, H->o.profile && l == 0);
             amgk::mz_prolong_sweep(s, v.A, f_fine, v.u, H->lv[l + 1].u, H->gl[l], H->d_geo_w[l],
                                    l1 ? v.l1 : nullptr, o.smooth_weight, v.u_alt);
          }
@@ -771,7 +705,7 @@ static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = f
          continue;
       }
       {
-         ProfScope ps(H, PROF_PROLONG0, s, l == 0);
+         AmgProfLog::Scope ps(H->prof, PROF_PROLONG0, s, H->o.profile && l == 0);
          if (H->geo[l])
             amgk::geo_prolong(s, H->gl[l], H->d_geo_w[l], H->lv[l + 1].u, v.u);
          else
@@ -800,7 +734,7 @@ static void bpx_cycle(amg_hier *H, bool precond)
    const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
    const amgk::Gemv pro_mode = amgk::gemv_mode(1.0, 1.0);
    for (int l = 0; l < L - 1; l++) {
-      ProfScope ps(H, PROF_RESTRICT0, s, l == 0);
+      AmgProfLog::Scope ps(H->prof, PROF_RESTRICT0, s, H->o.profile && l == 0);
       amgk::spgemv(s, H->lv[l].R, l == 0 ? H->r0 : H->lv[l].f, nullptr, mv, H->lv[l + 1].f, 0,
                    H->lv[l + 1].n, nullptr);
    }
@@ -819,7 +753,7 @@ static void bpx_cycle(amg_hier *H, bool precond)
    }
    for (int l = L - 2; l >= 0; l--) {
       double *ef = (l == 0) ? H->e0 : H->lv[l].u;
-      ProfScope ps(H, PROF_PROLONG0, s, l == 0);
+      AmgProfLog::Scope ps(H->prof, PROF_PROLONG0, s, H->o.profile && l == 0);
       amgk::spgemv(s, H->lv[l].P, H->lv[l + 1].u, ef, pro_mode, ef, 0, H->lv[l].n, nullptr);
    }
    if (precond)
@@ -1047,7 +981,7 @@ static int outer_residual(amg_hier *H, int slot)
          }
       }
       {
-         ProfScope ps(H, PROF_OUTER, c->stream);
+         AmgProfLog::Scope ps(H->prof, PROF_OUTER, c->stream, H->o.profile);
          if (c->fuse_outer == 3)
             outer_slabs(H, p, skip_r);
          else
@@ -1064,7 +998,7 @@ static int outer_residual(amg_hier *H, int slot)
       return AMG_OK;
    }
    {
-      ProfScope ps(H, PROF_OUTER, c->stream);
+      AmgProfLog::Scope ps(H->prof, PROF_OUTER, c->stream, H->o.profile);
       if (reuse_applies(H)) {
          const bool l1 = (H->o.smoother == AMG_L1_JACOBI);
          const bool skip_r = H->o.reuse_outer_residual >= 2;
@@ -1474,7 +1408,7 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    AMG_ARG(sched >= AMG_SCHED_FREE && sched <= AMG_SCHED_TIMED, "amg_async_solve: async_schedule %d", sched);
    AMG_ARG(!conv_global || sched == AMG_SCHED_FREE || sched == AMG_SCHED_ROUND_ROBIN || sched == AMG_SCHED_TIMED,
            "amg_async_solve: a sequential schedule needs converge_test_type LOCAL");
-   AMG_ARG(sched != AMG_SCHED_TIMED || ((int)H->async_dur.size() >= L && (int)H->async_t.size() >= L),
+   AMG_ARG(sched != AMG_SCHED_TIMED || H->race.timed_ready(L),
            "amg_async_solve: AMG_SCHED_TIMED needs amg_hier_set_async_durations / _times");
    AMG_TRY(solve_begin(H, f, u));
    Level &v0 = H->lv[0];
@@ -1515,19 +1449,17 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          AMG_TRY(dalloc(H, n0, &a.g_y));
          AMG_TRY(dalloc(H, n0, &a.g_r));
       }
-      if (!a.ev_a) {
-         AMG_HIP(hipEventCreateWithFlags(&a.ev_a, hipEventDisableTiming));
-         AMG_HIP(hipEventCreateWithFlags(&a.ev_b, hipEventDisableTiming));
-      }
+      AMG_TRY(a.ev_a.create(hipEventDisableTiming));
+      AMG_TRY(a.ev_b.create(hipEventDisableTiming));
    }
-   hipEvent_t ready, t_start;
-   AMG_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-   AMG_HIP(hipEventCreate(&t_start));
-   H->corr.reset(L);
+   AmgEvent ready, t_start;
+   AMG_TRY(ready.create(hipEventDisableTiming));
+   AMG_TRY(t_start.create());
+   H->race.corr.reset(L);
    // the free race's update windows on the device clock (amg_async_update_windows)
    const bool rec0 = sched == AMG_SCHED_FREE && !(c->graphs && !semi && !read_res && !global_res && !H->o.profile &&
                                                    (o.delay_type == AMG_DELAY_NONE || o.delay_usec <= 0));
-   if (rec0 && H->corr.stamps_begin(c->stream, L, std::max(1, o.num_cycles) * (conv_global ? 16 : 1) + 1, n0))
+   if (rec0 && H->race.corr.stamps_begin(c->stream, L, std::max(1, o.num_cycles) * (conv_global ? 16 : 1) + 1, n0))
       return amg_set_error(AMG_ERR_OOM, "amg_async_solve: update-window stamps");
    AMG_HIP(hipEventRecord(ready, c->stream));
    AMG_HIP(hipEventRecord(t_start, c->stream));
@@ -1547,9 +1479,6 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    // SEMI_ASYNC update stream (the lock of :238-283)
    hipStream_t us = sched != AMG_SCHED_FREE ? lstream(k_lo) : c->comm_stream;
    std::vector<int> issued(L, 0);
-   // converge GLOBAL under round robin: the correction about to run is the
-   // group's last (it sees the converge flag at its barrier)
-   bool rr_last = false;
    // graphs of the level corrections (ctx->graphs): the FULL_ASYNC / READ_SOL /
    // LOCAL-residual correction issues the same kernels with the same
    // arguments every time (no delays, no profiling events), so each level's
@@ -1559,8 +1488,9 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    // free race without graphs: record each correction's update point (the
    // atomic add / the exclusive update of the shared vectors) as its end event
    const bool rec = sched == AMG_SCHED_FREE && !graphs;
-   // one correction of level k, issued on its stream
-   auto correction = [&](int k) -> int {
+   // one correction of level k, issued on its stream; last: it is the group's
+   // last (converge GLOBAL: it sees the converge flag at its barrier)
+   auto correction = [&](int k, bool last) -> int {
       hipStream_t s = lstream(k);
       AddLevel &a = H->al[k];
       auto to_update = [&]() -> int {
@@ -1574,7 +1504,7 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          return AMG_OK;
       };
       const int grb = gr[k], gre = gr[k + 1];
-      unsigned long long *stp = rec ? H->corr.stamp(k, issued[k]) : nullptr;
+      unsigned long long *stp = rec ? H->race.corr.stamp(k, issued[k]) : nullptr;
       {
          // injected delay of the threads this level group stands for
          const int T = delay_threads(o), g = k - k_lo;
@@ -1604,11 +1534,11 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
             amgk::res_update(us, H->r0, a.y, a.y_fine, n0, 0);
             AMG_TRY(from_update());
          } else {
-            if (rec && H->corr.record_start(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
+            if (rec && H->race.corr.record_start(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
             amgk::vaxpy(s, 1.0, a.e[0], a.f_acc, 0, n0);
             amgk::res_update(s, H->r0, a.y, a.y_fine, n0, 1, stp);
          }
-         if (rec && H->corr.record(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
+         if (rec && H->race.corr.record(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
       } else {
          if (semi) {
             AMG_TRY(to_update());
@@ -1616,10 +1546,10 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
             amgk::semi_correct(us, v0.u, a.e[0], a.u_priv, n0);
             AMG_TRY(from_update());
          } else if (!fused) {
-            if (rec && H->corr.record_start(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
+            if (rec && H->race.corr.record_start(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
             amgk::atomic_correct(s, v0.u, a.e[0], a.u_priv, n0, stp);
          }
-         if (rec && H->corr.record(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
+         if (rec && H->race.corr.record(k, issued[k], s)) return amg_set_error(AMG_ERR_HIP, "correction event");
          if (!global_res) {
             // SMEM_Residual(A0, f, u_k, y, r_k): y = A u_k; r = f - y (one pass, y unused)
             amgk::residual_fsub(s, v0.A, a.u_priv, v0.f, a.y, a.y_fine, n0);
@@ -1629,8 +1559,7 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
       // GLOBAL residual update (SMEM_Async_AMG.cpp:353-356): converge LOCAL's
       // N-th correction does not touch the shared residual
       // (converge GLOBAL: the correction whose barrier sees the flag, known
-      // only under the round-robin schedule)
-      const bool last = conv_global ? rr_last : issued[k] + 1 >= o.num_cycles;
+      // only under a deterministic schedule)
       if (global_res && !last) {
          // :356-414: u_k = u; the level's slice of r = f - A u_k (SMEM_Residual:
          // y = A u_k, then r = f - y) into the shared r; then r_k = r (under the
@@ -1648,8 +1577,8 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    };
    if (graphs) graphs_check(H);
    if (graphs && (int)H->g_lev.size() != L) graphs_reset(H);
-   auto run = [&](int k) -> int {
-      if (!graphs) return correction(k);
+   auto run = [&](int k, bool last) -> int {
+      if (!graphs) return correction(k, last);
       hipStream_t s = lstream(k);
       if (H->g_lev_s[k] != s) {
          if (H->g_lev[k]) hipGraphExecDestroy(H->g_lev[k]);
@@ -1657,105 +1586,25 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          H->g_lev_s[k] = s;
       }
       bool warm = H->g_lev_warm[k] != 0;
-      const int st = graph_issue(H->g_lev[k], warm, s, [&] { return correction(k); });
+      const int st = graph_issue(H->g_lev[k], warm, s, [&] { return correction(k, last); });
       H->g_lev_warm[k] = warm ? 1 : 0;
       return st;
    };
-   if (sched == AMG_SCHED_FINEST_FIRST || sched == AMG_SCHED_COARSEST_FIRST) {
-      // the level groups one after another (or_set_async_schedule 1 / 2)
-      for (int q = 0; q < ngrp; q++) {
-         const int k = sched == AMG_SCHED_FINEST_FIRST ? k_lo + q : k_hi - 1 - q;
-         for (int cyc = 0; cyc < o.num_cycles; cyc++) {
-            AMG_TRY(run(k));
-            issued[k]++;
-         }
-      }
-   } else if (sched == AMG_SCHED_ROUND_ROBIN && conv_global) {
-      // round robin under converge GLOBAL (or_set_async_schedule 3): the
-      // finest group's root raises the converge flag after its update once
-      // every group (the idle coarsest group of the reference too, which
-      // keeps the same count) has num_cycles corrections; a group stops at
-      // the first of its own updates that sees the flag (Misc.cpp:418-441)
-      std::vector<int> stopped(L, 0);
-      bool flag = false;
-      for (int left = ngrp; left > 0;)
-         for (int k = k_lo; k < k_hi; k++) {
-            if (stopped[k]) continue;
-            // k_lo raises the flag after its update (counted with this
-            // correction); the correction that sees it is the group's last
-            bool raise = false;
-            if (k == k_lo && !flag) {
-               bool all = true;
-               for (int l = k_lo; l < k_hi; l++)
-                  if (issued[l] + (l == k ? 1 : 0) < o.num_cycles) all = false;
-               // the reference's idle coarsest group runs its turn after the
-               // last correcting level, so in round r it has r - 1 when k_lo checks
-               if (k_hi < L && issued[k_lo] < o.num_cycles) all = false;
-               raise = all;
-            }
-            rr_last = flag || raise;
-            AMG_TRY(run(k));
-            rr_last = false;
-            issued[k]++;
-            if (raise) flag = true;
-            if (flag) {
-               stopped[k] = 1;
-               left--;
-            }
-         }
-   } else if (sched == AMG_SCHED_TIMED) {
-      // the race at fixed level speeds (or_set_async_schedule 4): level k's
-      // j-th correction ends at j * dur[k]; whole corrections in the order of
-      // their end times, ties to the finer level.  The reference's idle
-      // coarsest group (LOCAL residuals: its correction is zero) takes its
-      // turns too, as a group that issues nothing -- under converge GLOBAL its
-      // count is part of the flag (the oracle's group L - 1).  Converge LOCAL:
-      // a group stops after num_cycles; GLOBAL: k_lo raises the flag after an
-      // update once every group has num_cycles, and each group stops at the
-      // first of its corrections that sees the flag (as under round robin)
-      const int kv = std::max(k_hi, L); // groups [k_lo, kv); k >= k_hi: idle
-      std::vector<int> cnt(kv, 0), stopped(kv, 0);
-      bool flag = false;
-      for (;;) {
-         int best = -1;
-         double tb = 0.0;
-         for (int k = k_lo; k < kv; k++) {
-            if (stopped[k]) continue;
-            const double t = amg_timed_end(H->async_t[k], H->async_dur[k], cnt[k]);
-            if (best < 0 || t < tb) best = k, tb = t;
-         }
-         if (best < 0) break;
-         bool raise = false;
-         if (conv_global && best == k_lo && !flag) {
-            raise = true;
-            for (int l = k_lo; l < kv; l++)
-               if (cnt[l] + (l == best ? 1 : 0) < o.num_cycles) raise = false;
-         }
-         if (best < k_hi) {
-            rr_last = flag || raise;
-            AMG_TRY(run(best));
-            rr_last = false;
-            issued[best]++;
-         }
-         cnt[best]++;
-         if (raise) flag = true;
-         if (conv_global ? flag : cnt[best] >= o.num_cycles) stopped[best] = 1;
-      }
-   } else if (!conv_global) {
-      // free race, or round robin under converge LOCAL (one stream: the
-      // cycle-major, level-minor issue order is the turn order)
-      for (int cyc = 0; cyc < o.num_cycles; cyc++)
-         for (int k = k_lo; k < k_hi; k++) {
-            AMG_TRY(run(k));
-            issued[k]++;
-         }
+   if (sched != AMG_SCHED_FREE || !conv_global) {
+      // a deterministic schedule's turn order; the free race under converge
+      // LOCAL issues in round-robin order (its streams do the racing)
+      AmgAsyncTurns turns(sched, k_lo, k_hi, L, o.num_cycles, conv_global, H->race);
+      int k;
+      for (bool last; turns.next(&k, &last); issued[k]++) AMG_TRY(run(k, last));
    } else {
       // run until every level has completed num_cycles corrections; faster
       // levels keep correcting meanwhile (at most 2 in flight per level)
       constexpr int DEPTH = 2;
-      std::vector<std::vector<hipEvent_t>> done(L, std::vector<hipEvent_t>(DEPTH));
-      for (auto &d : done)
-         for (auto &e : d) AMG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      std::vector<AmgEvent> done[DEPTH];
+      for (auto &d : done) {
+         d.resize(L);
+         for (auto &e : d) AMG_TRY(e.create(hipEventDisableTiming));
+      }
       std::vector<int> completed(L, 0);
       const long long cap = 1000LL * std::max(1, o.num_cycles);
       int st = AMG_OK;
@@ -1764,7 +1613,7 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          for (int k = k_lo; k < k_hi && st == AMG_OK; k++) {
             while (completed[k] < issued[k]) {
                // not ready: still pending; any other status is a device error
-               const hipError_t q = hipEventQuery(done[k][completed[k] % DEPTH]);
+               const hipError_t q = hipEventQuery(done[completed[k] % DEPTH][k]);
                if (q == hipErrorNotReady) break;
                if (q != hipSuccess) {
                   st = amg_set_error(AMG_ERR_HIP, "amg_async_solve: level %d correction: %s", k,
@@ -1779,8 +1628,9 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          bool progressed = false;
          for (int k = k_lo; k < k_hi && st == AMG_OK; k++) {
             if (issued[k] - completed[k] < DEPTH && issued[k] < cap) {
-               if ((st = run(k)) != AMG_OK) break;
-               const hipError_t er = hipEventRecord(done[k][issued[k] % DEPTH], c->level_streams[k]);
+               // no correction of a free race is known to be its group's last
+               if ((st = run(k, false)) != AMG_OK) break;
+               const hipError_t er = hipEventRecord(done[issued[k] % DEPTH][k], c->level_streams[k]);
                if (er != hipSuccess) {
                   st = amg_set_error(AMG_ERR_HIP, "amg_async_solve: hipEventRecord: %s", hipGetErrorString(er));
                   break;
@@ -1793,14 +1643,12 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
          if (!progressed) std::this_thread::yield();
       }
       for (int k = k_lo; k < k_hi; k++) hipStreamSynchronize(c->level_streams[k]);
-      for (auto &d : done)
-         for (auto &e : d) hipEventDestroy(e);
       if (st != AMG_OK) return st;
    }
    // each level's finish (its stream after its last correction)
-   std::vector<hipEvent_t> t_end(L, nullptr);
+   std::vector<AmgEvent> t_end(L);
    for (int k = k_lo; k < k_hi; k++) {
-      AMG_HIP(hipEventCreate(&t_end[k]));
+      AMG_TRY(t_end[k].create());
       AMG_HIP(hipEventRecord(t_end[k], c->level_streams[k]));
       AMG_HIP(hipStreamWaitEvent(c->stream, t_end[k], 0));
    }
@@ -1808,7 +1656,6 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    AMG_HIP(hipStreamWaitEvent(c->stream, ready, 0));
    if (read_res && !semi)
       for (int k = k_lo; k < k_hi; k++) amgk::vaxpy(c->stream, 1.0, H->al[k].f_acc, v0.u, 0, n0); // :416-426
-   AMG_HIP(hipEventDestroy(ready));
    AMG_TRY(outer_residual(H, 1));
    AMG_HIP(hipMemcpyAsync(c->h_pinned, H->d_hist + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    amgk::vcopy(c->stream, v0.u, u->d, 0, n0);
@@ -1816,65 +1663,44 @@ extern "C" int amg_async_solve(amg_hier *H, const amg_vec *f, amg_vec *u, int *l
    if (relres) *relres = c->h_pinned[0] / H->r0norm;
    if (level_corrections)
       for (int k = 0; k < L; k++) level_corrections[k] = issued[k];
-   if (sched == AMG_SCHED_FREE && H->corr.collect(t_start, issued))
+   if (sched == AMG_SCHED_FREE && H->race.corr.collect(t_start, issued))
       return amg_set_error(AMG_ERR_HIP, "amg_async_solve: correction times");
-   if (rec0 && H->corr.stamps_collect(issued, c->wall_khz))
+   if (rec0 && H->race.corr.stamps_collect(issued, c->wall_khz))
       return amg_set_error(AMG_ERR_HIP, "amg_async_solve: update-window stamps");
-   H->level_ms.assign(L, 0.0);
+   H->race.level_ms.assign(L, 0.0);
    for (int k = k_lo; k < k_hi; k++) {
       float ms = 0.f;
       // one stream under a deterministic schedule: a level's last correction
       // is not its stream's last work, so only the free race is timed
       if (sched == AMG_SCHED_FREE) AMG_HIP(hipEventElapsedTime(&ms, t_start, t_end[k]));
-      H->level_ms[k] = ms;
-      AMG_HIP(hipEventDestroy(t_end[k]));
+      H->race.level_ms[k] = ms;
    }
-   AMG_HIP(hipEventDestroy(t_start));
    return AMG_OK;
 }
 
 extern "C" int amg_hier_set_async_durations(amg_hier *H, const double *ms, int n)
 {
    AMG_ARG(H && ms && n >= H->L, "amg_hier_set_async_durations: need %d levels", H ? H->L : 0);
-   for (int k = 0; k < H->L; k++) AMG_ARG(ms[k] > 0.0, "amg_hier_set_async_durations: level %d: %g", k, ms[k]);
-   H->async_dur.assign(ms, ms + H->L);
-   H->async_t.assign(H->L, {});
-   return AMG_OK;
+   return H->race.set_durations("amg_hier_set_async_durations", ms, H->L);
 }
 
 extern "C" int amg_hier_set_async_times(amg_hier *H, const double *t, const int *n, int nlev)
 {
    AMG_ARG(H && t && n && nlev >= H->L, "amg_hier_set_async_times: need %d levels", H ? H->L : 0);
-   H->async_t.assign(H->L, {});
-   H->async_dur.assign(H->L, 1.0);
-   for (int k = 0, off = 0; k < H->L; off += n[k], k++) {
-      AMG_ARG(n[k] >= 0, "amg_hier_set_async_times: level %d: %d entries", k, n[k]);
-      H->async_t[k].assign(t + off, t + off + n[k]);
-   }
-   return AMG_OK;
+   return H->race.set_times("amg_hier_set_async_times", t, n, H->L);
 }
 
 extern "C" int amg_async_correction_ms(const amg_hier *H, int level, double *ms, int cap, int *count)
 {
    AMG_ARG(H && count && level >= 0 && level < H->L, "amg_async_correction_ms: bad argument");
-   const bool start = cap < 0; // cap < 0: the update windows' start times, -cap entries
-   if (start) cap = -cap;
-   const auto &vv = start ? H->corr.ms0 : H->corr.ms;
-   const auto &v = level < (int)vv.size() ? vv[level] : std::vector<double>();
-   *count = (int)v.size();
-   for (int j = 0; j < (int)v.size() && j < cap && ms; j++) ms[j] = v[j];
+   H->race.correction_ms(level, ms, cap, count);
    return AMG_OK;
 }
 
 extern "C" int amg_async_update_windows(const amg_hier *H, int level, double *ms, int cap, int *count)
 {
    AMG_ARG(H && count && level >= 0 && level < H->L, "amg_async_update_windows: bad argument");
-   const bool start = cap < 0; // cap < 0: the windows' starts, -cap entries
-   if (start) cap = -cap;
-   const auto &vv = start ? H->corr.w0 : H->corr.w1;
-   const auto &v = level < (int)vv.size() ? vv[level] : std::vector<double>();
-   *count = (int)v.size();
-   for (int j = 0; j < (int)v.size() && j < cap && ms; j++) ms[j] = v[j];
+   H->race.update_windows(level, ms, cap, count);
    return AMG_OK;
 }
 
@@ -1882,14 +1708,44 @@ extern "C" int amg_async_update_rows(const amg_hier *H, int level, int corr, dou
 {
    AMG_ARG(H && count && level >= 0 && level < H->L && corr >= 0,
            "amg_async_update_rows: bad argument");
-   *count = H->corr.rows_of(level, corr, ms, cap < 0 ? -cap : cap, cap < 0);
+   H->race.update_rows(level, corr, ms, cap, count);
    return AMG_OK;
 }
 
 extern "C" int amg_async_level_ms(const amg_hier *H, double *ms)
 {
    AMG_ARG(H && ms, "amg_async_level_ms: null argument");
-   AMG_ARG(!H->level_ms.empty(), "amg_async_level_ms: no asynchronous solve yet");
-   for (int k = 0; k < H->L; k++) ms[k] = H->level_ms[k];
+   return H->race.copy_level_ms("amg_async_level_ms", ms, H->L);
+}
+
+// the turn order of a schedule without a solve (the deterministic schedules'
+// order is host logic, checked against the oracle on the CPU): the groups
+// AmgAsyncTurns yields with level speeds dur[ngroups] (null: all 1), or end
+// times t / tn as amg_hier_set_async_times takes them, into seq / last (the
+// first cap of *count turns) and every group's count into group_counts[ngroups]
+extern "C" int amg_async_turns_probe(int sched, int k_lo, int k_hi, int ngroups, int num_cycles, int conv_global,
+                                     const double *dur, const double *t, const int *tn, int *seq, int *last, int cap,
+                                     int *count, int *group_counts)
+{
+   AMG_ARG(sched >= AMG_SCHED_FINEST_FIRST && sched <= AMG_SCHED_TIMED && 0 <= k_lo && k_lo < k_hi && count,
+           "amg_async_turns_probe: bad argument");
+   AMG_ARG(!conv_global || sched == AMG_SCHED_ROUND_ROBIN || sched == AMG_SCHED_TIMED,
+           "amg_async_turns_probe: a sequential schedule needs converge_test_type LOCAL");
+   const int G = std::max(k_hi, ngroups);
+   AmgRaceRecord race;
+   const std::vector<double> ones(G, 1.0);
+   if (t && tn)
+      AMG_TRY(race.set_times("amg_async_turns_probe", t, tn, G));
+   else
+      AMG_TRY(race.set_durations("amg_async_turns_probe", dur ? dur : ones.data(), G));
+   AmgAsyncTurns turns(sched, k_lo, k_hi, G, num_cycles, conv_global != 0, race);
+   int k;
+   *count = 0;
+   for (bool l; turns.next(&k, &l); ++*count)
+      if (*count < cap) {
+         if (seq) seq[*count] = k;
+         if (last) last[*count] = l;
+      }
+   if (group_counts) std::copy(turns.cnt.begin(), turns.cnt.end(), group_counts);
    return AMG_OK;
 }

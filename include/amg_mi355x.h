@@ -385,6 +385,17 @@ int amg_matvec_timed(amg_ctx *ctx, const amg_mat *A, const amg_vec *x, amg_vec *
  * WRITE_SIZE calibration (tools/pmc_traffic.py) */
 int amg_stream_triad(amg_ctx *ctx, long long n, int reps, double *gbs);
 int amg_pmc_calib(amg_ctx *ctx, int mode, long long bytes);
+/* test helper (host only, no device needed): the turn order amg_async_solve /
+ * amg_dist_async_solve issue under a deterministic async_schedule, from the
+ * solves' own generator.  Groups [k_lo, k_hi) correct, groups [k_hi, ngroups)
+ * are the reference's idle ones; AMG_SCHED_TIMED takes the level speeds
+ * dur[ngroups] (NULL: all 1) or, where t and tn are given, the end times as
+ * amg_hier_set_async_times takes them.  seq / last (nullable) receive the
+ * first cap turns' groups and last-correction flags, *count the number of
+ * turns, group_counts[ngroups] (nullable) every group's corrections */
+int amg_async_turns_probe(int sched, int k_lo, int k_hi, int ngroups, int num_cycles, int conv_global,
+                          const double *dur, const double *t, const int *tn, int *seq, int *last, int cap,
+                          int *count, int *group_counts);
 /* setup arrays: L1_row_norm SMEM_Setup.cpp:222-232, A_diag :234-237 */
 int amg_l1_norms(amg_ctx *ctx, const amg_mat *A, amg_vec *out);
 int amg_a_diag(amg_ctx *ctx, const amg_mat *A, double omega, amg_vec *out);
