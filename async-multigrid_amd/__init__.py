@@ -417,6 +417,53 @@ class Hier:
         check(lib.amg_eigs_power(self.h, iters, C.byref(emax), C.byref(emin)))
         return emax.value, emin.value
 
+    def precond_apply(self, r, z=None):
+        """z = M^-1 r, one cycle of this hierarchy's solver from a zero state (amg_precond_apply).
+        Vec in, Vec out (z given or created, no host sync); an array in, an array out."""
+        if isinstance(r, Vec):
+            zv = Vec(self.ctx, self.n0) if z is None else z
+            check(lib.amg_precond_apply(self.h, r.h, zv.h))
+            return zv
+        rv, zv = self.ctx.vec(r), Vec(self.ctx, self.n0)
+        check(lib.amg_precond_apply(self.h, rv.h, zv.h))
+        out = zv.download()
+        rv.free()
+        zv.free()
+        return out
+
+    def pcg_solve(self, f, x0=None):
+        """AMG-preconditioned CG (amg_pcg_solve): returns (x, residual-norm history, iterations)."""
+        fv = f if isinstance(f, Vec) else self.ctx.vec(f)
+        xv = self.ctx.vec(np.zeros(self.n0) if x0 is None else x0)
+        hist = np.zeros(self.opts.num_cycles + 1)
+        k = C.c_int()
+        check(lib.amg_pcg_solve(self.h, fv.h, xv.h, _dp(hist), C.byref(k)))
+        x = xv.download()
+        return x, hist[:k.value + 1], k.value
+
+    def pcg_start(self, f, x0):
+        r0 = C.c_double()
+        check(lib.amg_pcg_start(self.h, f.h, x0.h, C.byref(r0)))
+        return r0.value
+
+    def pcg_iterate(self, k):
+        check(lib.amg_pcg_iterate(self.h, k))
+
+    def pcg_resnorm(self):
+        r = C.c_double()
+        check(lib.amg_pcg_resnorm(self.h, C.byref(r)))
+        return r.value
+
+    def pcg_get_x(self, out):
+        check(lib.amg_pcg_get_x(self.h, out.h))
+
+    def pcg_scalars(self, cap=4096):
+        """(alpha, beta, rho) of the last min(iterations, cap, 4096) iterations, oldest first."""
+        a, b, r = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        n = C.c_int()
+        check(lib.amg_pcg_scalars(self.h, _dp(a), _dp(b), _dp(r), int(cap), C.byref(n)))
+        return a[:n.value], b[:n.value], r[:n.value]
+
     def profile(self, reset=True):
         ms = np.zeros(5)
         n = np.zeros(5, dtype=np.int64)

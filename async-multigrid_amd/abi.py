@@ -171,6 +171,13 @@ PROTOTYPES = {
     "amg_async_update_windows": (_i, [_p, _i, _dp, _i, _ip]),
     "amg_async_update_rows": (_i, [_p, _i, _i, _dp, _i, _ip]),
     "amg_eigs_power": (_i, [_p, _i, _dp, _dp]),
+    "amg_precond_apply": (_i, [_p, _p, _p]),
+    "amg_pcg_solve": (_i, [_p, _p, _p, _dp, _ip]),
+    "amg_pcg_start": (_i, [_p, _p, _p, _dp]),
+    "amg_pcg_iterate": (_i, [_p, _i]),
+    "amg_pcg_resnorm": (_i, [_p, _dp]),
+    "amg_pcg_get_x": (_i, [_p, _p]),
+    "amg_pcg_scalars": (_i, [_p, _dp, _dp, _dp, _i, _ip]),
     "amg_hier_profile_read": (_i, [_p, _dp, _llp, _i]),
     "amg_gen_create": (_i, [_i, _i, _i, _i, _i, _i, _pp]),
     "amg_gen_free": (_i, [_p]),

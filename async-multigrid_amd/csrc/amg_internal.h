@@ -465,6 +465,24 @@ void dot_partials(hipStream_t s, const double *x, const double *y, int n, double
 void reduce_partials(hipStream_t s, const double *partials, int np, double *out, int do_sqrt,
                      double *scratch);
 
+// preconditioned CG (amg_pcg.hip): the device scalar block sc and the kernels
+// that read and write it; np <= 1024 partials of the reduction grid
+enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_PQ = 3, PCG_RR = 4, PCG_NSCALARS = 8 };
+// pq = sum(part); sc[ALPHA] = sc[RHO] / pq (0 where pq = 0), also into *ring_alpha
+void pcg_alpha(hipStream_t s, const double *part, int np, double *sc, double *ring_alpha);
+// *norm = sqrt(sum(part_rr)); rho' = sum(part_rz); sc[BETA] = rho' / sc[RHO] (0 where
+// rho = 0), sc[RHO] = rho', both also into the rings; first: sc[RHO] = rho' only
+void pcg_beta(hipStream_t s, const double *part_rr, const double *part_rz, int np, double *sc, double *norm,
+              double *ring_beta, double *ring_rho, int first);
+// x += sc[ALPHA] p; r -= sc[ALPHA] q; partials of r.r in dot_partials' order.  u0 != null: also
+// the zero-guess sweep of A (n rows) on the new r into u0 -- jacobi_zero variant 0 on a cleared
+// u0: w r / a_ii where a_ii != 0 and 0 elsewhere, or r / l1
+void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
+                   const double *sc, double *partials, int *nparts, const amg_mat *A = nullptr,
+                   const double *l1 = nullptr, double w = 0.0, double *u0 = nullptr);
+// p = z + sc[BETA] p
+void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc);
+
 } // namespace amgk
 
 // process-wide lock held by the teardown entry points (amg_api.cpp)

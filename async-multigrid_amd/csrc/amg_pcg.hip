@@ -1,0 +1,181 @@
+// amg_pcg.hip -- the preconditioned conjugate-gradient recurrence's own kernels
+// (amg_pcg_* in amg_solver.cpp).  alpha, beta and rho never leave the device:
+// a single-workgroup kernel finishes each dot product and forms the quotient
+// in the same launch, and the vector kernels read the scalars from device
+// memory.  Every product and sum is rounded on its own (-ffp-contract=off), the
+// quotients are IEEE divisions, and the three dot products are summed in
+// amg_vec_dot's order: red_blocks(n) workgroups of 256 lanes, lane t of
+// workgroup b adding i = 256 b + t, += 256 gridDim; block_sum_256's tree; the
+// workgroup partials through the same lane-strided sum in one workgroup.
+#include <algorithm>
+
+#include "amg_internal.h"
+
+namespace amgk {
+
+// amg_kernels.hip's reduction grid and workgroup tree (the sums must come out
+// with the bits of partials_k / sum_partials_k)
+static inline int pcg_red_blocks(int n) { return std::max(1, std::min(1024, (n + 2047) / 2048)); }
+
+__device__ __forceinline__ double pcg_block_sum_256(double v, double *lds4)
+{
+#pragma unroll
+   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+   __syncthreads();
+   if (lane == 0) lds4[wid] = v;
+   __syncthreads();
+   double s = 0.0;
+   if (threadIdx.x == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+   return s;
+}
+
+// sum of p[0..np) in sum_partials_k<<<1, 256>>>'s order (valid in thread 0)
+__device__ __forceinline__ double pcg_sum_partials(const double *__restrict__ p, int np, double *lds4)
+{
+   double s = 0.0;
+   for (int i = threadIdx.x; i < np; i += 256) s += p[i];
+   return pcg_block_sum_256(s, lds4);
+}
+
+// pq = sum(part); alpha = rho / pq (0 where pq = 0: a zero right-hand side)
+__global__ __launch_bounds__(256) void pcg_alpha_k(const double *__restrict__ part, int np,
+                                                   double *__restrict__ sc, double *__restrict__ ring_alpha)
+{
+   __shared__ double red[4];
+   const double pq = pcg_sum_partials(part, np, red);
+   if (threadIdx.x == 0) {
+      const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
+      sc[PCG_PQ] = pq;
+      sc[PCG_ALPHA] = alpha;
+      if (ring_alpha) *ring_alpha = alpha;
+   }
+}
+
+// ||r|| = sqrt(sum(part_rr)) into *norm; rho' = sum(part_rz); beta = rho' / rho
+// (0 where rho = 0); rho = rho'.  first: the start of a solve (rho only)
+__global__ __launch_bounds__(256) void pcg_beta_k(const double *__restrict__ part_rr,
+                                                  const double *__restrict__ part_rz, int np,
+                                                  double *__restrict__ sc, double *__restrict__ norm,
+                                                  double *__restrict__ ring_beta, double *__restrict__ ring_rho,
+                                                  int first)
+{
+   __shared__ double red[4];
+   const double rr = pcg_sum_partials(part_rr, np, red);
+   const double rz = pcg_sum_partials(part_rz, np, red);
+   if (threadIdx.x == 0) {
+      *norm = sqrt(rr);
+      sc[PCG_RR] = rr;
+      if (!first) {
+         const double rho = sc[PCG_RHO];
+         const double beta = rho != 0.0 ? rz / rho : 0.0;
+         sc[PCG_BETA] = beta;
+         *ring_beta = beta;
+         *ring_rho = rz;
+      }
+      sc[PCG_RHO] = rz;
+   }
+}
+
+// the cycle's zero-guess Jacobi sweep on the new residual, written where r is
+// still in registers (jacobi_zero variant 0 on a cleared u: u = w r / a for
+// a != 0, 0 otherwise; u = r / l1 for L1 Jacobi)
+struct PcgZero {
+   double *u;          // null: not fused
+   const double *diag; // a_ii (null: the uniform value a)
+   const double *l1;
+   double a, w;
+};
+
+__device__ __forceinline__ void pcg_zero_sweep(const PcgZero &zg, long long i, double ri)
+{
+   if (zg.l1) {
+      zg.u[i] = ri / zg.l1[i];
+   } else {
+      const double a = zg.diag ? zg.diag[i] : zg.a;
+      zg.u[i] = a != 0.0 ? zg.w * ri / a : 0.0;
+   }
+}
+
+// x += alpha p;  r -= alpha q;  the partials of r.r on the reduction grid.  Four
+// grid strides are loaded ahead; a lane still adds its squares in index order.
+template <bool ZG>
+__global__ __launch_bounds__(256) void pcg_xr_k(double *__restrict__ x, const double *__restrict__ p,
+                                                double *__restrict__ r, const double *__restrict__ q, int n,
+                                                const double *__restrict__ sc, double *__restrict__ partials,
+                                                PcgZero zg)
+{
+   __shared__ double red[4];
+   const double alpha = sc[PCG_ALPHA];
+   const long long st = (long long)gridDim.x * 256;
+   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+   double s = 0.0;
+   for (; i + 3 * st < n; i += 4 * st) {
+      double xv[4], pv[4], rv[4], qv[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+         xv[k] = x[i + k * st];
+         pv[k] = p[i + k * st];
+         rv[k] = r[i + k * st];
+         qv[k] = q[i + k * st];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+         x[i + k * st] = xv[k] + alpha * pv[k];
+         const double ri = rv[k] - alpha * qv[k];
+         r[i + k * st] = ri;
+         if (ZG) pcg_zero_sweep(zg, i + k * st, ri);
+         s += ri * ri;
+      }
+   }
+   for (; i < n; i += st) {
+      x[i] = x[i] + alpha * p[i];
+      const double ri = r[i] - alpha * q[i];
+      r[i] = ri;
+      if (ZG) pcg_zero_sweep(zg, i, ri);
+      s += ri * ri;
+   }
+   s = pcg_block_sum_256(s, red);
+   if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// p = z + beta p
+__global__ __launch_bounds__(256) void pcg_p_k(const double *__restrict__ z, double *__restrict__ p, int n,
+                                               const double *__restrict__ sc)
+{
+   const double beta = sc[PCG_BETA];
+   const long long st = (long long)gridDim.x * 256;
+   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += st) p[i] = z[i] + beta * p[i];
+}
+
+void pcg_alpha(hipStream_t s, const double *part, int np, double *sc, double *ring_alpha)
+{
+   pcg_alpha_k<<<1, 256, 0, s>>>(part, np, sc, ring_alpha);
+}
+
+void pcg_beta(hipStream_t s, const double *part_rr, const double *part_rz, int np, double *sc, double *norm,
+              double *ring_beta, double *ring_rho, int first)
+{
+   pcg_beta_k<<<1, 256, 0, s>>>(part_rr, part_rz, np, sc, norm, ring_beta, ring_rho, first);
+}
+
+void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
+                   const double *sc, double *partials, int *nparts, const amg_mat *A, const double *l1, double w,
+                   double *u0)
+{
+   const int nb = pcg_red_blocks(n);
+   if (u0) {
+      const PcgZero zg{u0, A->diag_uni ? nullptr : A->diag, l1, A->diag_u, w};
+      pcg_xr_k<true><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, zg);
+   } else {
+      pcg_xr_k<false><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, PcgZero{});
+   }
+   *nparts = nb;
+}
+
+void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc)
+{
+   if (n > 0) pcg_p_k<<<std::min((n + 255) / 256, 1024), 256, 0, s>>>(z, p, n, sc);
+}
+
+} // namespace amgk

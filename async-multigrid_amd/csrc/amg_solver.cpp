@@ -114,6 +114,17 @@ struct amg_hier {
    // delay / fault injection: one generator per reference thread (srand(tid),
    // SMEM_Solve.cpp:113), reset by every solve
    std::vector<unsigned long long> delay_rng;
+   // preconditioned CG (amg_pcg_*): r lives in r0 and z in lv[0].u, where the
+   // cycle reads and leaves them; x, p, q (n0 each), the device scalar block,
+   // the r.r and p.q / r.z partials and the alpha / beta / rho rings are
+   // allocated by the first amg_pcg_start
+   struct Pcg {
+      double *x = nullptr, *p = nullptr, *q = nullptr, *sc = nullptr, *part_rr = nullptr, *part_dot = nullptr,
+             *ring = nullptr;
+      int iter = 0;
+      bool on = false;
+      double r0norm = 0.0;
+   } pcg;
    std::vector<void *> allocs;
    AmgProfLog prof;
 };
@@ -632,7 +643,9 @@ static bool smooth_all_levels(amg_hier *H, hipStream_t s, int Alevel, const doub
 // ---- SMEM_Sync_Parfor_Vcycle (SMEM_Sync_AMG.cpp:8-145) -------------------------
 // defer_post: leave level 0's last post-smoothing sweep to outer_residual,
 // which runs it fused with the outer residual (mz_sweep_outer)
-static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = false)
+// zero0_done: level 0's zero-guess pre-sweep is already in lv[0].u (the PCG
+// residual update wrote it: same bits)
+static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = false, bool zero0_done = false)
 {
    hipStream_t s = H->ctx->stream;
    const amg_opts &o = H->o;
@@ -645,6 +658,7 @@ static void vcycle(amg_hier *H, bool precond, bool reuse_r0, bool defer_post = f
       return e ? std::atoi(e) != 0 : true;
    }();
    for (auto &lv : H->lv) lv.zero_done = false;
+   H->lv[0].zero_done = zero0_done;
    for (int l = 0; l < L - 1; l++) {
       Level &v = H->lv[l];
       v.zero_flag = 1;
@@ -1021,6 +1035,7 @@ static void init_vectors(amg_hier *H)
 {
    // Misc.cpp:565-692 InitVectors / InitSolve
    hipStream_t s = H->ctx->stream;
+   H->pcg.on = false; // r0 and lv[0].u (PCG's r and z) belong to the new solve
    for (int l = 0; l < H->L; l++) {
       Level &v = H->lv[l];
       if (l > 0) amgk::vset(s, v.f, 0.0, 0, v.n);
@@ -1312,6 +1327,252 @@ extern "C" int amg_eigs_power(amg_hier *H, int iters, double *eig_max, double *e
       }
    }
    AMG_HIP(hipStreamSynchronize(c->stream));
+   return AMG_OK;
+}
+
+// ---- preconditioned CG (-outer_solver pcg: DMEM_Main.cpp:788-804, --------------
+// DMEM_Setup.cpp:129-165, SMEM_Main.cpp:702-722) ----------------------------------
+// HYPRE's two-norm PCG with one cycle of H's solver from a zero guess as M^-1:
+// the multiplicative V-cycle or the BPX cycle in preconditioner mode, or one
+// synchronous additive cycle (u := 0, f_0 := r).  The recurrence, every
+// statement a separately rounded fp64 operation:
+//    r = f - A x0;  z = M^-1 r;  p = z;  rho = r.z;  hist[0] = sqrt(r.r)
+//    q = A p;  alpha = rho / p.q;  x += alpha p;  r -= alpha q;  hist[k] = sqrt(r.r)
+//    z = M^-1 r;  rho' = r.z;  beta = rho' / rho;  rho = rho';  p = z + beta p
+// (alpha, beta = 0 where their divisor is 0: a zero right-hand side stays zero).
+// r lives in r0, where every cycle reads its right-hand side and none writes,
+// and z is lv[0].u, where the cycle leaves it: the preconditioner costs no
+// copy.  Where the cycle's first level-0 sweep is the zero-guess Jacobi sweep on
+// r (pcg_fuse_zero), the residual update writes it as well, so the cycle neither
+// clears u nor reads r again.  cheby_flag, delays, graph replay and
+// reuse_outer_residual do not apply.
+constexpr int PCG_RING = 4096; // alpha / beta / rho of the last PCG_RING iterations
+
+static int pcg_check(const amg_hier *H, const char *who)
+{
+   const int sv = H->o.solver;
+   AMG_ARG(sv == AMG_MULT || sv == AMG_BPX || sv == AMG_MULTADD || sv == AMG_AFACX,
+           "%s: solver %d cannot precondition CG (MULT, BPX, MULTADD and AFACX hierarchies only; the "
+           "asynchronous solvers are not a fixed operator)", who, sv);
+   AMG_ARG(sv != AMG_BPX || H->e0, "%s: the hierarchy was not created as BPX", who);
+   AMG_ARG(is_all_levels(H->o) == !H->al.empty(), "%s: the hierarchy was not created for this solver", who);
+   return AMG_OK;
+}
+
+// can the residual update write level 0's zero-guess pre-sweep (pcg_update_xr)?
+// A MULT cycle whose level 0 starts with jacobi_zero on r0
+static bool pcg_fuse_zero(const amg_hier *H)
+{
+   const amg_opts &o = H->o;
+   return o.solver == AMG_MULT && H->L > 1 && o.num_pre_smooth_sweeps >= 1 &&
+          (o.smoother == AMG_JACOBI || o.smoother == AMG_SYMM_JACOBI || o.smoother == AMG_L1_JACOBI);
+}
+
+// lv[0].u = M^-1 r0 (r0 is left as it is).  zero0_done: lv[0].u already holds
+// the cycle's first level-0 sweep on r0 (pcg_fuse_zero)
+static int pcg_precond(amg_hier *H, bool zero0_done = false)
+{
+   hipStream_t s = H->ctx->stream;
+   const amg_opts &o = H->o;
+   H->pre_ready = false;
+   H->r0_stale = false;
+   H->post_deferred = false;
+   H->have_state = false; // the stationary solve's u and r0 are overwritten
+   if (is_all_levels(o)) {
+      amgk::vset(s, H->lv[0].u, 0.0, 0, H->lv[0].n);
+      sync_add_vcycle(H);
+   } else {
+      for (int l = zero0_done ? 1 : 0; l < H->L; l++) {
+         amgk::vset(s, H->lv[l].u, 0.0, 0, H->lv[l].n);
+         H->lv[l].zero_flag = 0;
+      }
+      if (o.solver == AMG_BPX) {
+         amgk::vset(s, H->e0, 0.0, 0, H->lv[0].n);
+         bpx_cycle(H, true);
+      } else if (H->L == 1) {
+         // a one-level cycle smooths its only level's own f: r0 stands in for it
+         std::swap(H->lv[0].f, H->r0);
+         vcycle(H, true, false);
+         std::swap(H->lv[0].f, H->r0);
+      } else {
+         vcycle(H, true, false, false, zero0_done);
+      }
+   }
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
+
+extern "C" int amg_precond_apply(amg_hier *H, const amg_vec *r, amg_vec *z)
+{
+   AMG_ARG(H && r && z, "amg_precond_apply: null argument");
+   AMG_ARG(r->n == H->lv[0].n && z->n == H->lv[0].n, "amg_precond_apply: vector size %d/%d vs %d", r->n, z->n,
+           H->lv[0].n);
+   AMG_TRY(pcg_check(H, "amg_precond_apply"));
+   for (auto &a : H->al) AMG_TRY(ensure_xfer_scratch(H, a));
+   hipStream_t s = H->ctx->stream;
+   H->pcg.on = false; // a running PCG's r and z are overwritten
+   amgk::vcopy(s, r->d, H->r0, 0, r->n);
+   AMG_TRY(pcg_precond(H));
+   amgk::vcopy(s, H->lv[0].u, z->d, 0, z->n);
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
+
+static int pcg_alloc(amg_hier *H)
+{
+   amg_hier::Pcg &g = H->pcg;
+   const size_t n = (size_t)H->lv[0].n;
+   if (!g.x) AMG_TRY(dalloc(H, n, &g.x));
+   if (!g.p) AMG_TRY(dalloc(H, n, &g.p));
+   if (!g.q) AMG_TRY(dalloc(H, n, &g.q));
+   if (!g.sc) AMG_TRY(dalloc(H, amgk::PCG_NSCALARS, &g.sc));
+   if (!g.part_rr) AMG_TRY(dalloc(H, 1024, &g.part_rr));
+   if (!g.part_dot) AMG_TRY(dalloc(H, 1024, &g.part_dot));
+   if (!g.ring) AMG_TRY(dalloc(H, 3 * (size_t)PCG_RING, &g.ring));
+   return AMG_OK;
+}
+
+static int pcg_hist_slot(const amg_hier *H) { return H->pcg.iter % (H->hist_cap - 1); }
+
+// rho (and beta) from r0 . lv[0].u, ||r|| into the history from the r.r partials
+static void pcg_finish_dots(amg_hier *H, int first)
+{
+   amg_hier::Pcg &g = H->pcg;
+   hipStream_t s = H->ctx->stream;
+   const int n = H->lv[0].n;
+   int np = 0;
+   amgk::dot_partials(s, H->r0, H->lv[0].u, n, g.part_dot, &np); // the r.r partials' grid too
+   const int slot = first ? 0 : (g.iter - 1) % PCG_RING;
+   amgk::pcg_beta(s, g.part_rr, g.part_dot, np, g.sc, H->d_hist + pcg_hist_slot(H), g.ring + PCG_RING + slot,
+                  g.ring + 2 * PCG_RING + slot, first);
+}
+
+extern "C" int amg_pcg_start(amg_hier *H, const amg_vec *f, const amg_vec *x0, double *r0norm)
+{
+   AMG_ARG(H && f && x0, "amg_pcg_start: null argument");
+   Level &v = H->lv[0];
+   AMG_ARG(f->n == v.n && x0->n == v.n, "amg_pcg_start: vector size %d/%d vs %d", f->n, x0->n, v.n);
+   AMG_TRY(pcg_check(H, "amg_pcg_start"));
+   for (auto &a : H->al) AMG_TRY(ensure_xfer_scratch(H, a));
+   AMG_TRY(pcg_alloc(H));
+   amg_ctx *c = H->ctx;
+   amg_hier::Pcg &g = H->pcg;
+   hipStream_t s = c->stream;
+   g.on = false;
+   g.iter = 0;
+   amgk::vcopy(s, x0->d, g.x, 0, v.n);
+   amgk::spgemv(s, v.A, g.x, f->d, amgk::gemv_mode(-1.0, 1.0), H->r0, 0, v.n, nullptr);
+   AMG_TRY(pcg_precond(H));
+   int np = 0;
+   amgk::sumsq_partials(s, H->r0, v.n, g.part_rr, &np);
+   pcg_finish_dots(H, 1);
+   amgk::vcopy(s, H->lv[0].u, g.p, 0, v.n);
+   AMG_HIP(hipGetLastError());
+   AMG_HIP(hipMemcpyAsync(c->h_pinned, H->d_hist, sizeof(double), hipMemcpyDeviceToHost, s));
+   AMG_HIP(hipStreamSynchronize(s));
+   g.r0norm = c->h_pinned[0];
+   g.on = true;
+   if (r0norm) *r0norm = g.r0norm;
+   return AMG_OK;
+}
+
+extern "C" int amg_pcg_iterate(amg_hier *H, int k)
+{
+   AMG_ARG(H && H->pcg.on, "amg_pcg_iterate: call amg_pcg_start (or amg_pcg_solve) first");
+   amg_hier::Pcg &g = H->pcg;
+   hipStream_t s = H->ctx->stream;
+   Level &v = H->lv[0];
+   const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
+   // the cycle's first level-0 sweep rides on the residual update where it is
+   // the zero-guess Jacobi sweep (one pass over r and one clear of u fewer)
+   const bool fz = pcg_fuse_zero(H);
+   const double *l1 = H->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr;
+   for (int i = 0; i < k; i++) {
+      int np = 0, np_rr = 0;
+      amgk::spgemv(s, v.A, g.p, nullptr, mv, g.q, 0, v.n, nullptr);
+      amgk::dot_partials(s, g.p, g.q, v.n, g.part_dot, &np);
+      amgk::pcg_alpha(s, g.part_dot, np, g.sc, g.ring + g.iter % PCG_RING);
+      amgk::pcg_update_xr(s, g.x, g.p, H->r0, g.q, v.n, g.sc, g.part_rr, &np_rr, v.A, l1, H->o.smooth_weight,
+                          fz ? v.u : nullptr);
+      g.iter++;
+      const int st = pcg_precond(H, fz);
+      if (st != AMG_OK) {
+         g.on = false;
+         return st;
+      }
+      pcg_finish_dots(H, 0);
+      amgk::pcg_update_p(s, H->lv[0].u, g.p, v.n, g.sc);
+   }
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
+
+extern "C" int amg_pcg_resnorm(amg_hier *H, double *out)
+{
+   AMG_ARG(H && out && H->pcg.on, "amg_pcg_resnorm: no PCG state");
+   amg_ctx *c = H->ctx;
+   AMG_HIP(hipMemcpyAsync(c->h_pinned, H->d_hist + pcg_hist_slot(H), sizeof(double), hipMemcpyDeviceToHost,
+                          c->stream));
+   AMG_HIP(hipStreamSynchronize(c->stream));
+   *out = c->h_pinned[0];
+   return AMG_OK;
+}
+
+extern "C" int amg_pcg_get_x(amg_hier *H, amg_vec *x)
+{
+   AMG_ARG(H && x && H->pcg.on && x->n == H->lv[0].n, "amg_pcg_get_x: bad argument or no PCG state");
+   amgk::vcopy(H->ctx->stream, H->pcg.x, x->d, 0, x->n);
+   AMG_HIP(hipStreamSynchronize(H->ctx->stream));
+   return AMG_OK;
+}
+
+extern "C" int amg_pcg_scalars(const amg_hier *H, double *alpha, double *beta, double *rho, int cap, int *count)
+{
+   AMG_ARG(H && count && cap >= 0 && H->pcg.on, "amg_pcg_scalars: bad argument or no PCG state");
+   const amg_hier::Pcg &g = H->pcg;
+   hipStream_t s = H->ctx->stream;
+   const int m = std::min(std::min(g.iter, cap), PCG_RING);
+   double *out[3] = {alpha, beta, rho};
+   for (int a = 0; a < 3; a++) {
+      if (!out[a]) continue;
+      // iterations iter - m + 1 .. iter, oldest first (the ring may wrap)
+      for (int j = 0; j < m;) {
+         const int slot = (g.iter - m + j) % PCG_RING;
+         const int run = std::min(m - j, PCG_RING - slot);
+         AMG_HIP(hipMemcpyAsync(out[a] + j, g.ring + a * PCG_RING + slot, run * sizeof(double),
+                                hipMemcpyDeviceToHost, s));
+         j += run;
+      }
+   }
+   AMG_HIP(hipStreamSynchronize(s));
+   *count = m;
+   return AMG_OK;
+}
+
+extern "C" int amg_pcg_solve(amg_hier *H, const amg_vec *f, amg_vec *x, double *reshist, int *iters_done)
+{
+   AMG_ARG(H && f && x, "amg_pcg_solve: null argument");
+   amg_ctx *c = H->ctx;
+   AMG_TRY(amg_pcg_start(H, f, x, nullptr));
+   const amg_hier::Pcg &g = H->pcg;
+   if (reshist) reshist[0] = g.r0norm;
+   int done = 0;
+   for (int k = 1; k <= H->o.num_cycles; k++) {
+      AMG_TRY(amg_pcg_iterate(H, 1));
+      done = k;
+      if (H->o.check_resnorm == 1) {
+         double rn;
+         AMG_TRY(amg_pcg_resnorm(H, &rn));
+         if (reshist) reshist[k] = rn;
+         if (rn / g.r0norm < H->o.tol) break;
+      }
+   }
+   // without the per-iteration read the history comes from the device ring
+   // in one copy (as long as it has not wrapped)
+   if (reshist && H->o.check_resnorm != 1 && done > 0 && done < H->hist_cap - 1)
+      AMG_HIP(hipMemcpyAsync(reshist + 1, H->d_hist + 1, done * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   AMG_TRY(amg_pcg_get_x(H, x));
+   if (iters_done) *iters_done = done;
    return AMG_OK;
 }
 

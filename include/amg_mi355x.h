@@ -532,6 +532,41 @@ int amg_async_update_windows(const amg_hier *H, int level, double *ms, int cap, 
 int amg_async_update_rows(const amg_hier *H, int level, int corr, double *ms, int cap, int *count);
 /* EigsPower SMEM_Cheby.cpp:410-518 with this hierarchy's V-cycle as M^{-1} */
 int amg_eigs_power(amg_hier *H, int iters, double *eig_max, double *eig_min);
+/* ---- AMG-preconditioned conjugate gradients (-outer_solver pcg:
+ * DMEM_Main.cpp:788-804, DMEM_Setup.cpp:129-165, SMEM_Main.cpp:702-722) ----------
+ * z = M^-1 r: one cycle of H's solver from a zero state -- the MULT V-cycle or
+ * the BPX cycle in preconditioner mode, or one synchronous MULTADD / AFACX
+ * cycle on f_0 = r, u = 0 (composed smoothed transfers honoured).  ASYNC_*
+ * hierarchies are refused (AMG_ERR_ARG).  Enqueued on the context's stream, no
+ * host sync.  It overwrites the state of a running amg_solve_* / amg_pcg_*. */
+int amg_precond_apply(amg_hier *H, const amg_vec *r, amg_vec *z);
+/* HYPRE PCG as the reference sets it up: two-norm, relative tolerance tol,
+ * at most num_cycles iterations, M^-1 as above; x holds the initial guess on
+ * entry and the iterate on return.  Every statement one rounded fp64
+ * operation, the dot products in amg_vec_dot's order:
+ *    r = f - A x;  z = M^-1 r;  p = z;  rho = r.z;  reshist[0] = sqrt(r.r)
+ *    q = A p;  alpha = rho / p.q;  x += alpha p;  r -= alpha q;  reshist[k] = sqrt(r.r)
+ *    z = M^-1 r;  rho' = r.z;  beta = rho' / rho;  rho = rho';  p = z + beta p
+ * (alpha / beta are 0 where p.q / rho is 0, so f = 0 leaves x as it was).
+ * check_resnorm == 1 reads ||r|| back every iteration and stops once
+ * reshist[k] / reshist[0] < tol; otherwise num_cycles iterations run without a
+ * host sync.  reshist holds num_cycles + 1 entries.  cheby_flag, delays, graph
+ * replay and reuse_outer_residual do not apply.  CG theory needs a symmetric
+ * positive definite M^-1: the Jacobi-family smoothers with num_pre == num_post
+ * sweeps give one; hybrid JGS and the Gauss-Seidel forms do not and are
+ * accepted at the caller's risk. */
+int amg_pcg_solve(amg_hier *H, const amg_vec *f, amg_vec *x, double *reshist, int *iters_done);
+/* split form: start = x0, the initial residual and direction (returns ||r0||);
+ * iterate enqueues k iterations with no host sync (alpha, beta, rho and ||r||
+ * stay on the device); resnorm = ||r||_2 of the recurrence residual after the
+ * last enqueued iteration (host sync); get_x copies the iterate out */
+int amg_pcg_start(amg_hier *H, const amg_vec *f, const amg_vec *x0, double *r0norm);
+int amg_pcg_iterate(amg_hier *H, int k);
+int amg_pcg_resnorm(amg_hier *H, double *out);
+int amg_pcg_get_x(amg_hier *H, amg_vec *x);
+/* alpha, beta and the new rho = r.z of the last *count = min(iterations done,
+ * cap, 4096) iterations, oldest first (null arrays are skipped; host sync) */
+int amg_pcg_scalars(const amg_hier *H, double *alpha, double *beta, double *rho, int cap, int *count);
 /* profile: accumulated device milliseconds and launch counts of the fine-level
 s * kernels since the last reset: [0] level-0 residual in the cycle, [1] level-0
  * smoother sweeps, [2] R_0 restriction, [3] P_0 prolongation, [4] outer residual
