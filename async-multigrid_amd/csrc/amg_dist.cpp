@@ -13,6 +13,12 @@
 // the same kernels as the single-GPU path on slab-local CSR whose column ids
 // were remapped to [owned | ghost] without reordering any row, so every row
 // sum keeps its order and the iterates are bit-identical to one GPU.
+//
+// The synchronous cycle below serves both forms of amg_dist_hier, the
+// row-partitioned [owned | ghost] CSR form built here and the z-slab form of
+// amg_slab.cpp.  The form shows in the operator helpers only: dm_segments /
+// dm_split (which rows overlap which exchange), level_restrict /
+// level_prolong_add (how a transfer launches) and lzero (a vector's extent).
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -259,12 +265,6 @@ void amgd::launch_sqrt(hipStream_t s, const double *in, double *out) { sqrt_to_k
 // ---------------------------------------------------------------------------
 // distributed matrix: slab-local rows, columns remapped to [owned | ghost]
 // ---------------------------------------------------------------------------
-
-
-namespace {
-
-} // namespace
-
 int amgd::dalloc(amg_dist_hier *D, size_t bytes, void **p)
 {
    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 8));
@@ -514,31 +514,110 @@ int halo_begin(amg_dist_hier *D, DistMat &M, double *x)
    return AMG_OK;
 }
 
-int halo_end(amg_dist_hier *D, DistMat &M)
+} // namespace
+
+// ---------------------------------------------------------------------------
+// operator launches on a DistMat of either form.  Vectors are passed by their
+// first owned row; a slab operator's rows and columns start sro / sco rows
+// before it (its ghost planes), the row form's at 0
+// ---------------------------------------------------------------------------
+void amgd::dm_spgemv(hipStream_t s, const DistMat &M, const double *x, const double *b, const amgk::Gemv &g,
+                     double *y, long long rb, long long re, double *partials)
 {
-   if (M.replicated_cols || M.peers.empty()) return AMG_OK;
-   AMG_HIP(hipStreamWaitEvent(D->ctx->stream, D->ev_comm, 0));
-   return AMG_OK;
+   amgk::spgemv(s, M.A, x - M.sco, b ? b - M.sro : nullptr, g, y - M.sro, (int)(M.sro + rb),
+                (int)(M.sro + re), partials);
 }
 
-// interior rows first (overlapping the exchange), boundary rows after it
-template <class F>
-int split_launch(amg_dist_hier *D, DistMat &M, double *x, F launch)
+void amgd::dm_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
+                     double omega, double *out, long long rb, long long re)
 {
-   AMG_TRY(halo_begin(D, M, x));
-   launch(M.b0, M.b1, 0);
-   AMG_TRY(halo_end(D, M));
-   const int t0 = amgk::tile_blocks(M.b0, M.b1);
-   launch(0, M.b0, t0);
-   launch(M.b1, M.nrows, t0 + amgk::tile_blocks(0, M.b0));
+   amgk::jacobi_sweep(s, M.A, f - M.sro, x - M.sco, l1 ? l1 - M.sro : nullptr, omega, out - M.sro,
+                      (int)(M.sro + rb), (int)(M.sro + re));
+}
+
+void amgd::dm_residual_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
+                              double omega, double *r, double *unext, long long rb, long long re,
+                              double *partials)
+{
+   amgk::residual_jacobi(s, M.A, f - M.sro, x - M.sco, l1 ? l1 - M.sro : nullptr, omega,
+                         r ? r - M.sro : nullptr, unext - M.sro, (int)(M.sro + rb), (int)(M.sro + re), partials);
+}
+
+const double *amgd::dm_diag(const DistMat &M) { return M.A->diag + M.sro; }
+
+namespace {
+
+// owned rows [rb, re) of a split launch and where their norm partials start
+struct Seg {
+   long long rb, re, poff;
+};
+
+long long tiles(long long n) { return (n + 255) / 256; }
+
+// the segments of a split launch over M, the interior one (no ghost column)
+// first; *xchg: x's ghosts are exchanged; *nparts: norm partials in total.
+// Each form keeps its own order and partial layout (they fix the summation
+// order of the residual norm):
+//   rows  [b0, b1) | [0, b0) | [b1, n), partials in that order, one per
+//         product tile (amgk::tile_blocks)
+//   slab  interior planes | bottom plane | top plane (A reaches one plane),
+//         partials laid out bottom | interior | top in 256-row tiles
+int dm_segments(const amg_dist_hier *D, const DistMat &M, Seg seg[3], bool *xchg, long long *nparts)
+{
+   const long long n = M.nrows;
+   if (!M.slab) {
+      const int t_in = amgk::tile_blocks(M.b0, M.b1), t_lo = amgk::tile_blocks(0, M.b0);
+      seg[0] = {M.b0, M.b1, 0};
+      seg[1] = {0, M.b0, t_in};
+      seg[2] = {M.b1, n, t_in + t_lo};
+      *xchg = !M.replicated_cols && !M.peers.empty();
+      *nparts = t_in + t_lo + amgk::tile_blocks(M.b1, M.nrows);
+      return 3;
+   }
+   const int me = D->ctx->xport->rank;
+   const long long P = M.cP;
+   const bool lo = M.nlo[me] > 0, hi = M.nhi[me] > 0;
+   const long long i0 = lo ? P : 0, i1 = hi ? n - P : n;
+   const long long t_lo = lo ? tiles(P) : 0, t_in = i1 > i0 ? tiles(i1 - i0) : 0;
+   int ns = 0;
+   seg[ns++] = {i0, i1, t_lo};
+   if (lo) seg[ns++] = {0, P, 0};
+   if (hi) seg[ns++] = {n - P, n, t_lo + t_in};
+   *xchg = lo || hi; // no ghost plane: one launch over every row, no exchange
+   *nparts = t_lo + t_in + (hi ? tiles(P) : 0);
+   return ns;
+}
+
+// room for the norm partials of a split launch over M (each form's own bound)
+size_t dm_partials_room(const amg_dist_hier *D, const DistMat &M)
+{
+   if (M.slab) return (size_t)tiles(M.nrows) + 8;
+   Seg seg[3];
+   bool xchg;
+   long long np;
+   dm_segments(D, M, seg, &xchg, &np);
+   return (size_t)np + 1;
+}
+
+// one operator application with x's ghost exchange (the row form's packed
+// halo, the slab form's planes) on the communication stream: the interior
+// rows first, overlapping it, the boundary rows after it.
+// launch(rb, re, partial offset) on owned rows
+template <class F>
+int dm_split(amg_dist_hier *D, DistMat &M, double *x, F launch, long long *nparts = nullptr)
+{
+   Seg seg[3];
+   bool xchg;
+   long long np;
+   const int ns = dm_segments(D, M, seg, &xchg, &np);
+   if (nparts) *nparts = np;
+   if (xchg) AMG_TRY(M.slab ? slab_xchg_begin(D, x, M) : halo_begin(D, M, x));
+   for (int i = 0; i < ns; i++) {
+      if (i == 1 && xchg) AMG_HIP(hipStreamWaitEvent(D->ctx->stream, D->ev_comm, 0));
+      if (seg[i].re > seg[i].rb) launch(seg[i].rb, seg[i].re, seg[i].poff);
+   }
    AMG_HIP(hipGetLastError());
    return AMG_OK;
-}
-
-int nparts(const DistMat &M)
-{
-   return amgk::tile_blocks(M.b0, M.b1) + amgk::tile_blocks(0, M.b0) +
-          amgk::tile_blocks(M.b1, M.nrows);
 }
 
 } // namespace
@@ -917,17 +996,17 @@ extern "C" int amg_dist_hier_local_rows(amg_dist_hier *D, int level, int *row0, 
 }
 
 // ---------------------------------------------------------------------------
-// cycle
+// synchronous cycle (both forms)
 // ---------------------------------------------------------------------------
 namespace {
 
 int d_spgemv(amg_dist_hier *D, DistMat &M, double *x, const double *b, const amgk::Gemv &g,
-             double *y, double *partials)
+             double *y, double *partials, long long *nparts = nullptr)
 {
    hipStream_t s = D->ctx->stream;
-   return split_launch(D, M, x, [&](int rb, int re, int poff) {
-      amgk::spgemv(s, M.A, x, b, g, y, rb, re, partials ? partials + poff : nullptr);
-   });
+   return dm_split(D, M, x, [&](long long rb, long long re, long long poff) {
+      dm_spgemv(s, M, x, b, g, y, rb, re, partials ? partials + poff : nullptr);
+   }, nparts);
 }
 
 bool d_reuse(const amg_dist_hier *D)
@@ -935,23 +1014,63 @@ bool d_reuse(const amg_dist_hier *D)
    return D->o.reuse_outer_residual && D->o.num_pre_smooth_sweeps > 0 && !dist_mult_accel(D);
 }
 
+// zero a level-l vector over the extent lvec2 gave it: the row form's owned +
+// ghost capacity, the slab form's ghost planes around the owned rows
+void lzero(amg_dist_hier *D, int l, double *p)
+{
+   const DLevel &v = D->lv[l];
+   if (D->slab)
+      amgk::vset(D->ctx->stream, p - v.sg.off(), 0.0, 0, (int)v.sg.ext_rows());
+   else
+      amgk::vset(D->ctx->stream, p, 0.0, 0, v.cap);
+}
+
+// the slab transfers' exchange of ghost planes, on the compute stream
+XchgFn main_xchg(amg_dist_hier *D)
+{
+   return [D](double *x, long long n, long long cP, const std::vector<int> &lo, const std::vector<int> &hi) {
+      return slab_xchg(D->ctx, D->ctx->stream, x, n, cP, lo, hi);
+   };
+}
+
+// r_{l+1} = R_l r into dst (level l + 1's owned rows, or the allgather slot);
+// zg: the slab form's geometric restriction also writes level l + 1's
+// zero-guess sweep
+int level_restrict(amg_dist_hier *D, int l, double *r, double *dst, const amgk::ZeroGuess &zg)
+{
+   hipStream_t s = D->ctx->stream;
+   if (D->slab) return slab_restrict(D, s, l, r, dst, main_xchg(D), zg);
+   return d_spgemv(D, D->lv[l].R, r, nullptr, amgk::gemv_mode(1.0, 0.0), dst, nullptr);
+}
+
+// u += P_l xc
+int level_prolong_add(amg_dist_hier *D, int l, double *xc, double *u)
+{
+   hipStream_t s = D->ctx->stream;
+   if (D->slab) return slab_prolong(D, s, l, xc, u, true, main_xchg(D));
+   return d_spgemv(D, D->lv[l].P, xc, u, amgk::gemv_mode(1.0, 1.0), u, nullptr);
+}
+
 // SMEM_Sync_Parfor_Jacobi on a distributed level (ping-pong)
-int d_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_reuse)
+int dist_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_reuse)
 {
    DLevel &v = D->lv[l];
    hipStream_t s = D->ctx->stream;
    const bool l1 = D->o.smoother == AMG_L1_JACOBI;
    for (int k = 0; k < sweeps; k++) {
       if (k == 0 && v.zero_flag == 1) {
-         amgk::jacobi_zero(s, v.A.A->diag, f, l1 ? v.l1 : nullptr, D->o.smooth_weight, v.u, 0, v.n, 0);
+         if (v.zero_done)
+            v.zero_done = false; // folded into the restriction that produced f (same bits)
+         else
+            amgk::jacobi_zero(s, dm_diag(v.A), f, l1 ? v.l1 : nullptr, D->o.smooth_weight, v.u, 0, v.n, 0);
       } else if (k == 0 && allow_reuse && D->pre_ready) {
          std::swap(v.u, v.u_alt);
          D->pre_ready = false;
       } else {
-         AmgProfLog::Scope pr(D->prof, 1, D->ctx->stream, D->o.profile && l == 0);
+         AmgProfLog::Scope pr(D->prof, 1, s, D->o.profile && l == 0);
          double *x = v.u, *out = v.u_alt;
-         AMG_TRY(split_launch(D, v.A, x, [&](int rb, int re, int) {
-            amgk::jacobi_sweep(s, v.A.A, f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, out, rb, re);
+         AMG_TRY(dm_split(D, v.A, x, [&](long long rb, long long re, long long) {
+            dm_jacobi(s, v.A, f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, out, rb, re);
          }));
          std::swap(v.u, v.u_alt);
       }
@@ -963,36 +1082,67 @@ int d_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_re
 // on the outer residual r0 from a zero level-0 guess (precond_flag, the form
 // DMEM_MultCycle takes with precond_zero_init_guess = 1) and leaves the
 // correction in lv[0].u
-int d_vcycle(amg_dist_hier *D, bool precond)
+int dist_vcycle(amg_dist_hier *D, bool precond)
 {
-   if (D->slab) return slab_vcycle(D, precond);
    amg_ctx *c = D->ctx;
    hipStream_t s = c->stream;
    const int L = D->L, Ld = D->Ld;
-   const amgk::Gemv res_mode = amgk::gemv_mode(-1.0, 1.0);
-   const amgk::Gemv mv_mode = amgk::gemv_mode(1.0, 0.0);
-   const amgk::Gemv pro_mode = amgk::gemv_mode(1.0, 1.0);
+   double *slot = D->gath_buf ? D->gath_buf + (size_t)D->gath_blk * c->xport->nranks : nullptr;
+   // a fold flag set by an earlier cycle that returned early (an error between
+   // the restriction and the level's smoothing) must not skip this cycle's sweep
+   for (auto &lv : D->lv) lv.zero_done = false;
    for (int l = 0; l < Ld && l < L - 1; l++) {
       DLevel &v = D->lv[l];
-      const double *fl = (l == 0 && precond) ? D->r0 : v.f;
+      double *fl = (l == 0 && precond) ? D->r0 : v.f;
       v.zero_flag = (l == 0 && !precond) ? 0 : 1;
-      AMG_TRY(d_smooth(D, l, fl, D->o.num_pre_smooth_sweeps, l == 0 && d_reuse(D)));
-      {
-         AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile && l == 0);
-         AMG_TRY(d_spgemv(D, v.A, v.u, fl, res_mode, v.r_fine, nullptr));
-      }
-      {
-         AmgProfLog::Scope pr(D->prof, 2, D->ctx->stream, D->o.profile && l == 0);
-         double *dst = (l + 1 < Ld) ? D->lv[l + 1].f : D->gath_buf + (size_t)D->gath_blk * c->xport->nranks;
-         AMG_TRY(d_spgemv(D, v.R, v.r_fine, nullptr, mv_mode, dst, nullptr));
-         if (l + 1 == Ld) {
-            // assemble the replicated level-Ld right-hand side on every rank
-            const int R = c->xport->nranks;
-            AMG_TRY(xp_allgather(c, s, dst, D->gath_buf, (long long)D->gath_blk * 8));
-            scatter_blocks_k<<<std::max(1, std::min(4096, (D->gath_blk * R + 255) / 256)), 256, 0, s>>>(
-               D->gath_buf, D->gath_blk, D->d_gcnt, D->d_gdsp, R, D->f_rep);
+      AMG_TRY(dist_smooth(D, l, fl, D->o.num_pre_smooth_sweeps, l == 0 && d_reuse(D)));
+      const bool to_rep = l + 1 == Ld;
+      double *dst = to_rep ? slot : D->lv[l + 1].f;
+      // a slab level l + 1 (not the coarsest) starts its pre-smoothing with the
+      // zero-guess sweep u = w f / a: a geometric restriction writes it with f
+      // (as the single-GPU V-cycle does, amg_solver.cpp vcycle)
+      amgk::ZeroGuess zg;
+      if (D->slab && zg_fold_on() && !to_rep && l + 1 < L - 1 && D->o.smoother == AMG_JACOBI &&
+          D->o.num_pre_smooth_sweeps >= 1) {
+         // the fold writes u_{l+1} / reads a_ii on the coarse rows both
+         // restrictions write: owned coarse planes [Ka, Kb) of level l + 1,
+         // indexed from its first owned row -- the level's own rows exactly
+         const DLevel &nx = D->lv[l + 1];
+         AMG_ARG(nx.sg.za == v.Ka && nx.sg.zb == v.Kb && (long long)nx.n == (long long)(v.Kb - v.Ka) * nx.sg.P &&
+                    nx.A.sro >= 0 && nx.A.sro + nx.n <= (long long)nx.A.A->nrows,
+                 "slab zero-guess fold: level %d owns planes [%d, %d) (%d rows, diag rows [%lld, +%d) of %d), "
+                 "the restriction writes [%d, %d)",
+                 l + 1, nx.sg.za, nx.sg.zb, nx.n, nx.A.sro, nx.n, nx.A.A->nrows, v.Ka, v.Kb);
+         if (v.geo) { // the SpMV restriction does not fold
+            zg.d = dm_diag(nx.A);
+            zg.w = D->o.smooth_weight;
+            zg.u = nx.u;
+            zg.hi = nx.n;
+            zg.err = c->d_err;
          }
       }
+      // the gather into the replicated levels: the row form times it with its
+      // restriction (category 2), the slab form outside the categories
+      const bool gather_timed = to_rep && !D->slab;
+      if (l == 0 && D->geo0) {
+         AmgProfLog::Scope pr(D->prof, 0, s, D->o.profile);
+         // the right-hand side's ghost planes: f's were exchanged at the solve's
+         // start; the outer residual (preconditioner mode) changes every cycle
+         if (precond) AMG_TRY(slab_xchg(c, s, fl, v.n, v.sg.P, D->rr_flo, D->rr_fhi));
+         AMG_TRY(s_res_restrict(D, fl, v.u, dst, v.Ka, zg)); // dst: coarse plane Ka first
+      } else {
+         {
+            AmgProfLog::Scope pr(D->prof, 0, s, D->o.profile && l == 0);
+            AMG_TRY(d_spgemv(D, v.A, v.u, fl, amgk::gemv_mode(-1.0, 1.0), v.r_fine, nullptr));
+         }
+         AmgProfLog::Scope pr(D->prof, 2, s, D->o.profile && l == 0);
+         AMG_TRY(level_restrict(D, l, v.r_fine, dst, zg));
+         if (gather_timed) AMG_TRY(s_gather(D, s, slot, D->gath_buf, D->f_rep));
+      }
+      // level l + 1 is a distributed level only below Ld (to_rep: the
+      // replicated tail, which has no DLevel -- D->lv holds Ld entries)
+      if (!to_rep) D->lv[l + 1].zero_done = zg.u != nullptr;
+      if (to_rep && !gather_timed) AMG_TRY(s_gather(D, s, slot, D->gath_buf, D->f_rep));
    }
    const double *u_rep = nullptr;
    if (Ld < L) {
@@ -1001,60 +1151,56 @@ int d_vcycle(amg_dist_hier *D, bool precond)
       // single distributed level: SMEM_Sync_Parfor_Vcycle smooths the coarsest
       DLevel &v = D->lv[L - 1];
       const double *fl = (L == 1 && precond) ? D->r0 : v.f;
-      AMG_TRY(d_smooth(D, L - 1, fl, D->o.num_pre_smooth_sweeps + D->o.num_post_smooth_sweeps, false));
+      AMG_TRY(dist_smooth(D, L - 1, fl, D->o.num_pre_smooth_sweeps + D->o.num_post_smooth_sweeps, false));
    }
    for (int l = std::min(Ld, L - 1) - 1; l >= 0; l--) {
       DLevel &v = D->lv[l];
       v.zero_flag = 0;
       {
-         AmgProfLog::Scope pr(D->prof, 3, D->ctx->stream, D->o.profile && l == 0);
+         AmgProfLog::Scope pr(D->prof, 3, s, D->o.profile && l == 0);
          double *xc = (l + 1 < Ld) ? D->lv[l + 1].u : const_cast<double *>(u_rep);
-         AMG_TRY(d_spgemv(D, v.P, xc, v.u, pro_mode, v.u, nullptr));
+         AMG_TRY(level_prolong_add(D, l, xc, v.u));
       }
-      AMG_TRY(d_smooth(D, l, (l == 0 && precond) ? D->r0 : v.f, D->o.num_post_smooth_sweeps, false));
+      AMG_TRY(dist_smooth(D, l, (l == 0 && precond) ? D->r0 : v.f, D->o.num_post_smooth_sweeps, false));
    }
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
-}
-
-int d_outer_residual(amg_dist_hier *D, int slot)
-{
-   if (D->slab) return slab_outer_residual(D, slot);
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   DLevel &v = D->lv[0];
-   double *p;
-   const int np = nparts(v.A);
-   AMG_TRY(amg_ctx_partials(c, np + 1, &p));
-   {
-      AmgProfLog::Scope pr(D->prof, 4, D->ctx->stream, D->o.profile);
-      if (d_reuse(D) && D->L > 1) {
-         const bool l1 = D->o.smoother == AMG_L1_JACOBI;
-         // reuse_outer_residual 2: the MULT cycle never reads r0 outside
-         // preconditioner mode (excluded by d_reuse), so it is not written
-         double *r0 = (D->o.reuse_outer_residual >= 2 && D->o.solver == AMG_MULT) ? nullptr : D->r0;
-         double *x = v.u, *un = v.u_alt;
-         AMG_TRY(split_launch(D, v.A, x, [&](int rb, int re, int poff) {
-            amgk::residual_jacobi(s, v.A.A, v.f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, r0,
-                                  un, rb, re, p + poff);
-         }));
-         D->pre_ready = true;
-      } else {
-         AMG_TRY(d_spgemv(D, v.A, dist_iterate(D), v.f, amgk::gemv_mode(-1.0, 1.0), D->r0, p));
-         D->pre_ready = false;
-      }
-   }
-   double *sum = D->d_hist + slot;
-   amgk::reduce_partials(s, p, np, sum, 0, c->d_scalars + 4096);
-   AMG_TRY(xp_allreduce(c, s, sum, 1));
-   sqrt_to_k<<<1, 1, 0, s>>>(sum, sum);
    AMG_HIP(hipGetLastError());
    return AMG_OK;
 }
 
 } // namespace
 
-int amgd::dist_outer_residual(amg_dist_hier *D, int slot) { return d_outer_residual(D, slot); }
+int amgd::dist_outer_residual(amg_dist_hier *D, int slot)
+{
+   amg_ctx *c = D->ctx;
+   hipStream_t s = c->stream;
+   DLevel &v = D->lv[0];
+   long long np = 0;
+   double *p;
+   AMG_TRY(amg_ctx_partials(c, dm_partials_room(D, v.A), &p));
+   {
+      AmgProfLog::Scope pr(D->prof, 4, s, D->o.profile);
+      if (d_reuse(D) && D->L > 1) {
+         const bool l1 = D->o.smoother == AMG_L1_JACOBI;
+         // reuse_outer_residual 2: the MULT cycle never reads r0 outside
+         // preconditioner mode (excluded by d_reuse), so it is not written
+         double *r0 = (D->o.reuse_outer_residual >= 2 && D->o.solver == AMG_MULT) ? nullptr : D->r0;
+         double *x = v.u, *un = v.u_alt;
+         AMG_TRY(dm_split(D, v.A, x, [&](long long rb, long long re, long long poff) {
+            dm_residual_jacobi(s, v.A, v.f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, r0, un, rb, re, p + poff);
+         }, &np));
+         D->pre_ready = true;
+      } else {
+         AMG_TRY(d_spgemv(D, v.A, dist_iterate(D), v.f, amgk::gemv_mode(-1.0, 1.0), D->r0, p, &np));
+         D->pre_ready = false;
+      }
+   }
+   double *sum = D->d_hist + slot;
+   amgk::reduce_partials(s, p, (int)np, sum, 0, c->d_scalars + 4096);
+   AMG_TRY(xp_allreduce(c, s, sum, 1));
+   launch_sqrt(s, sum, sum);
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
 
 bool amgd::dist_mult_accel(const amg_dist_hier *D)
 {
@@ -1083,24 +1229,29 @@ bool amgd::AccelState::next(const amg_opts &o, double *om1, double *omd)
 
 int amgd::dist_solve_begin(amg_dist_hier *D, const double *f_local)
 {
-   if (D->slab) return slab_solve_begin(D, f_local);
    amg_ctx *c = D->ctx;
-   for (auto &v : D->lv) {
-      for (double *p : {v.f, v.u, v.u_alt, v.r_fine}) amgk::vset(c->stream, p, 0.0, 0, v.cap);
+   hipStream_t s = c->stream;
+   for (int l = 0; l < D->Ld; l++) {
+      DLevel &v = D->lv[l];
+      for (double *p : {v.f, v.u, v.u_alt, v.r_fine}) lzero(D, l, p);
       v.zero_flag = 0;
    }
-   AMG_TRY(h2d(c->stream, D->lv[0].f, f_local, (size_t)D->lv[0].n * sizeof(double)));
+   DLevel &v0 = D->lv[0];
+   if (D->slab) lzero(D, 0, D->r0);
+   AMG_TRY(h2d(s, v0.f, f_local, (size_t)v0.n * sizeof(double)));
+   // the fused level-0 residual + restriction reads f's ghost planes
+   if (D->geo0) AMG_TRY(slab_xchg(c, s, v0.f, v0.n, v0.sg.P, D->rr_flo, D->rr_fhi));
    // InitVectors on the replicated levels (the coarsest iterate carries over
    // between cycles, so a new solve starts it from zero as one GPU does)
    if (D->coarse) AMG_TRY(amg_hier_reset(D->coarse));
    if (D->x_acc) {
-      amgk::vset(c->stream, D->x_acc, 0.0, 0, D->lv[0].cap);
-      amgk::vset(c->stream, D->d_acc, 0.0, 0, std::max(1, D->lv[0].n));
+      lzero(D, 0, D->x_acc);
+      amgk::vset(s, D->d_acc, 0.0, 0, std::max(1, v0.n));
    }
    D->acc.reset(D->o);
    D->iter = 0;
-   AMG_TRY(d_outer_residual(D, 0));
-   AMG_TRY(d2h(c->stream, c->h_pinned, D->d_hist, sizeof(double)));
+   AMG_TRY(dist_outer_residual(D, 0));
+   AMG_TRY(d2h(s, c->h_pinned, D->d_hist, sizeof(double)));
    D->r0norm = c->h_pinned[0];
    D->have_state = true;
    return AMG_OK;
@@ -1136,15 +1287,15 @@ extern "C" int amg_dist_solve_iterate(amg_dist_hier *D, int k)
          // DMEM_Mult.cpp:40-55: e = 0; e = M r; x += e; ChebyUpdate(d, e); x += d
          DLevel &v = D->lv[0];
          amgk::vset(D->ctx->stream, v.u, 0.0, 0, v.n);
-         AMG_TRY(d_vcycle(D, true));
+         AMG_TRY(dist_vcycle(D, true));
          double om1 = 0.0, omd = 0.0;
          const bool upd = D->acc.next(D->o, &om1, &omd);
          amgk::dmem_mult_accel(D->ctx->stream, D->x_acc, v.u, D->d_acc, v.n, upd ? 0 : 1, om1, omd);
       } else {
-         AMG_TRY(d_vcycle(D, false));
+         AMG_TRY(dist_vcycle(D, false));
       }
       D->iter++;
-      AMG_TRY(d_outer_residual(D, D->iter % (D->hist_cap - 1)));
+      AMG_TRY(dist_outer_residual(D, D->iter % (D->hist_cap - 1)));
    }
    return AMG_OK;
 }
@@ -1179,9 +1330,7 @@ extern "C" int amg_dist_profile_read(amg_dist_hier *D, double *ms, long long *la
 extern "C" int amg_dist_fine_spmv(amg_dist_hier *D, int reps, double *ms)
 {
    AMG_ARG(D && ms && reps >= 1, "amg_dist_fine_spmv: bad argument");
-   if (D->slab) return slab_fine_spmv(D, reps, ms);
-   amg_ctx *c = D->ctx;
    DLevel &v = D->lv[0];
    const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   return amg_timed_reps(c->stream, reps, [&] { return d_spgemv(D, v.A, v.u, nullptr, mv, v.r_fine, nullptr); }, ms);
+   return amg_timed_reps(D->ctx->stream, reps, [&] { return d_spgemv(D, v.A, v.u, nullptr, mv, v.r_fine, nullptr); }, ms);
 }

@@ -130,10 +130,7 @@ int a_spgemv(amg_dist_hier *D, AsyncLevel &a, DistMat &M, double *x, const doubl
              const amgk::Gemv &g, double *y)
 {
    AMG_TRY(a_halo(D, a, M, x));
-   if (M.slab)
-      slab_spgemv(a.s, M, x, b, g, y, 0, M.nrows, nullptr);
-   else
-      amgk::spgemv(a.s, M.A, x, b, g, y, 0, M.nrows, nullptr);
+   dm_spgemv(a.s, M, x, b, g, y, 0, M.nrows, nullptr);
    return AMG_OK;
 }
 
@@ -161,7 +158,7 @@ int apply_A(amg_dist_hier *D, AsyncLevel &a, int l, double *x, const double *b, 
 
 const double *diag_of(const amg_dist_hier *D, int l)
 {
-   if (l < D->Ld) return D->slab ? slab_diag(D->lv[l].A) : D->lv[l].A.A->diag;
+   if (l < D->Ld) return dm_diag(D->lv[l].A);
    return D->cA[l - D->Ld]->diag;
 }
 
@@ -337,10 +334,7 @@ int a_smooth(amg_dist_hier *D, AsyncLevel &a, int l, const double *f, double *u,
          if (l < D->Ld) {
             DistMat &M = D->lv[l].A;
             AMG_TRY(a_halo(D, a, M, a.u_prev));
-            if (M.slab)
-               slab_jacobi(s, M, f, a.u_prev, l1v, omega, u, 0, n);
-            else
-               amgk::jacobi_sweep(s, M.A, f, a.u_prev, l1v, omega, u, 0, n);
+            dm_jacobi(s, M, f, a.u_prev, l1v, omega, u, 0, n);
          } else {
             amgk::jacobi_sweep(s, D->cA[l - D->Ld], f, a.u_prev, l1v, omega, u, 0, n);
          }

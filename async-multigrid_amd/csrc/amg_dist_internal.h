@@ -1,6 +1,11 @@
-// amg_dist_internal.h -- shared internals of the multi-GPU solve phase
-// (amg_dist.cpp: transport, plans, synchronous cycle; amg_dist_async.cpp:
-// asynchronous additive cycle).  Not part of the C-ABI.
+// amg_dist_internal.h -- shared internals of the multi-GPU solve phase.
+//   amg_dist.cpp        transport, the row form's plans and construction, the
+//                       operator launches on a DistMat (dm_*) and the one
+//                       synchronous cycle of both forms
+//   amg_slab.cpp        the z-slab form: construction, plane exchange, its
+//                       transfers and the fused level-0 residual + restriction
+//   amg_dist_async.cpp  asynchronous additive cycle
+// Not part of the C-ABI.
 #pragma once
 
 #include <rccl/rccl.h>
@@ -252,18 +257,26 @@ int dvec(amg_dist_hier *D, size_t n, double **p);
 // both levels la and lb (scratch used on either)
 int lvec(amg_dist_hier *D, int l, double **p);
 int lvec2(amg_dist_hier *D, int la, int lb, double **p);
+// ---- operator launches on a DistMat (amg_dist.cpp) ----
+// launches on owned rows [rb, re) of a distributed operator of either form (no
+// exchange; vectors by their first owned row): y = alpha A x + beta b, ...
+void dm_spgemv(hipStream_t s, const DistMat &M, const double *x, const double *b, const amgk::Gemv &g,
+               double *y, long long rb, long long re, double *partials);
+void dm_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
+               double omega, double *out, long long rb, long long re);
+// ... and amgk::residual_jacobi (r may be null)
+void dm_residual_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
+                        double omega, double *r, double *unext, long long rb, long long re, double *partials);
+// the diagonal of the owned rows
+const double *dm_diag(const DistMat &M);
 // ---- slab hierarchies (amg_slab.cpp) ----
 // plane exchange of x's ghost planes for an operator with per-rank needs
 // nlo / nhi (planes of cP rows below / above each rank's n_own owned rows)
 int slab_xchg(amg_ctx *c, hipStream_t s, double *x, long long n_own, long long cP, const std::vector<int> &nlo,
               const std::vector<int> &nhi);
-// y = alpha A x + beta b on owned rows [rb, re) of a slab operator (no exchange)
-void slab_spgemv(hipStream_t s, const DistMat &M, const double *x, const double *b, const amgk::Gemv &g,
-                 double *y, long long rb, long long re, double *partials);
-void slab_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
-                 double omega, double *out, long long rb, long long re);
-// the diagonal of the owned rows
-const double *slab_diag(const DistMat &M);
+// the exchange of x's ghost planes for M on the communication stream, ordered
+// after the compute stream's work so far; the caller waits on D->ev_comm
+int slab_xchg_begin(amg_dist_hier *D, double *x, const DistMat &M);
 // level-l transfers of a slab hierarchy on stream s, ghost planes exchanged
 // by xchg(x, M-like needs); restrict: dst = level l+1 owned rows (or the
 // allgather slot when l + 1 is replicated); prolong: out = P_l x (add = false)
@@ -273,11 +286,16 @@ using XchgFn = std::function<int(double *x, long long n_own, long long cP, const
 int slab_restrict(amg_dist_hier *D, hipStream_t s, int l, double *r, double *dst, const XchgFn &xchg,
                   amgk::ZeroGuess zg = amgk::ZeroGuess());
 int slab_prolong(amg_dist_hier *D, hipStream_t s, int l, double *x, double *out, bool add, const XchgFn &xchg);
-// sync cycle pieces of slab hierarchies (amg_dist.cpp dispatches to them)
-int slab_vcycle(amg_dist_hier *D, bool precond);
-int slab_outer_residual(amg_dist_hier *D, int slot);
-int slab_solve_begin(amg_dist_hier *D, const double *f_local);
-int slab_fine_spmv(amg_dist_hier *D, int reps, double *ms);
+// slab steps of the synchronous cycle: whether a level's zero-guess sweep is
+// folded into the restriction that writes its f (AMG_ZG_FOLD_SLAB); the fused
+// level-0 residual + restriction f_1 = R_0 (f - A_0 u) on the owned coarse
+// planes (dst's first plane is dcz0), overlapping u's exchange
+bool zg_fold_on();
+int s_res_restrict(amg_dist_hier *D, const double *f, double *u, double *dst, int dcz0,
+                   amgk::ZeroGuess zg = amgk::ZeroGuess());
+// every rank's restricted rows (slot) allgathered into gath and scattered into
+// the replicated level's full vector (either form)
+int s_gather(amg_dist_hier *D, hipStream_t s, double *slot, double *gath, double *full);
 // shared construction pieces (amg_dist.cpp)
 int dist_check_opts(const amg_opts *o);
 void structured_planes(const amg_gen *g, int R, std::vector<std::vector<int>> &z0);

@@ -19,8 +19,9 @@
 // communication stream while the compute stream runs the planes that read no
 // ghost (DMEM's finestIntra ghost exchange, DMEM_Comm.cpp:81-348 /
 // CreateCommData_LocalRes DMEM_Setup.cpp:666-1265, and hypre's ParCSR halo
-// inside hypre_ParCSRMatrixMatvec).  The cycle is SMEM_Sync_Parfor_Vcycle
-// (SMEM_Sync_AMG.cpp:8-145) with SMEM_Solve's outer loop (SMEM_Solve.cpp:128-240).
+// inside hypre_ParCSRMatrixMatvec).  The synchronous cycle is the one both
+// forms run (amg_dist.cpp dist_vcycle); this file holds the slab form's
+// construction, exchange, transfers and fused level-0 residual + restriction.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -145,12 +146,10 @@ int geo_weights(const amg_gen *g, int l, amgk::GeoT &t, bool *ok)
    return AMG_OK;
 }
 
-long long tiles(long long n) { return (n + 255) / 256; }
-
 } // namespace
 
 // ---------------------------------------------------------------------------
-// exchange and slab operator launches
+// exchange and the slab steps of the synchronous cycle (amg_dist.cpp)
 // ---------------------------------------------------------------------------
 int amgd::slab_xchg(amg_ctx *c, hipStream_t s, double *x, long long n_own, long long cP, const std::vector<int> &nlo,
                     const std::vector<int> &nhi)
@@ -180,28 +179,10 @@ int amgd::slab_xchg(amg_ctx *c, hipStream_t s, double *x, long long n_own, long 
    return xp_p2p(c, s, np, peers, sp, sb, rp, rb);
 }
 
-void amgd::slab_spgemv(hipStream_t s, const DistMat &M, const double *x, const double *b, const amgk::Gemv &g,
-                       double *y, long long rb, long long re, double *partials)
-{
-   amgk::spgemv(s, M.A, x - M.sco, b ? b - M.sro : nullptr, g, y - M.sro, (int)(M.sro + rb),
-                (int)(M.sro + re), partials);
-}
-
-void amgd::slab_jacobi(hipStream_t s, const DistMat &M, const double *f, const double *x, const double *l1,
-                       double omega, double *out, long long rb, long long re)
-{
-   amgk::jacobi_sweep(s, M.A, f - M.sro, x - M.sco, l1 ? l1 - M.sro : nullptr, omega, out - M.sro,
-                      (int)(M.sro + rb), (int)(M.sro + re));
-}
-
-const double *amgd::slab_diag(const DistMat &M) { return M.A->diag + M.sro; }
-
-namespace {
-
 // RCCL exchange of x's ghost planes on the communication stream, ordered
 // after everything the compute stream issued before (no pack kernel: the
 // planes are contiguous); the caller waits on D->ev_comm
-int xchg_begin(amg_dist_hier *D, double *x, const DistMat &M)
+int amgd::slab_xchg_begin(amg_dist_hier *D, double *x, const DistMat &M)
 {
    amg_ctx *c = D->ctx;
    AMG_HIP(hipEventRecord(D->ev_pack, c->stream));
@@ -211,41 +192,9 @@ int xchg_begin(amg_dist_hier *D, double *x, const DistMat &M)
    return AMG_OK;
 }
 
-// a square slab operator (reach one plane): the owned planes that read no
-// ghost first, overlapping the exchange, then the one or two boundary planes.
-// launch(rb, re, partial offset) on owned rows; the norm partials of the
-// segments are laid out bottom plane, interior, top plane (*nparts in total)
-template <class F>
-int split_A(amg_dist_hier *D, const DistMat &M, double *x, F launch, long long *nparts = nullptr)
-{
-   const int me = D->ctx->xport->rank;
-   const long long P = M.cP, n = M.nrows;
-   const bool lo = M.nlo[me] > 0, hi = M.nhi[me] > 0;
-   if (!lo && !hi) {
-      launch(0LL, n, 0LL);
-      if (nparts) *nparts = tiles(n);
-      return AMG_OK;
-   }
-   AMG_TRY(xchg_begin(D, x, M));
-   const long long i0 = lo ? P : 0, i1 = hi ? n - P : n;
-   const long long t_lo = lo ? tiles(P) : 0, t_in = i1 > i0 ? tiles(i1 - i0) : 0;
-   if (i1 > i0) launch(i0, i1, t_lo);
-   AMG_HIP(hipStreamWaitEvent(D->ctx->stream, D->ev_comm, 0));
-   if (lo) launch(0LL, P, 0LL);
-   if (hi) launch(n - P, n, t_lo + t_in);
-   if (nparts) *nparts = t_lo + t_in + (hi ? tiles(P) : 0);
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
-}
-
-bool s_reuse(const amg_dist_hier *D)
-{
-   return D->o.reuse_outer_residual && D->o.num_pre_smooth_sweeps > 0 && !dist_mult_accel(D);
-}
-
 // the slab levels' zero-guess sweeps folded into their restrictions (as the
 // single-GPU V-cycle does; AMG_ZG_FOLD_SLAB=0 turns it off)
-bool zg_fold_on()
+bool amgd::zg_fold_on()
 {
    static const bool on = [] {
       const char *e = std::getenv("AMG_ZG_FOLD_SLAB");
@@ -254,31 +203,7 @@ bool zg_fold_on()
    return on;
 }
 
-int s_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow_reuse)
-{
-   DLevel &v = D->lv[l];
-   hipStream_t s = D->ctx->stream;
-   const bool l1 = D->o.smoother == AMG_L1_JACOBI;
-   for (int k = 0; k < sweeps; k++) {
-      if (k == 0 && v.zero_flag == 1) {
-         if (v.zero_done)
-            v.zero_done = false; // folded into the restriction that produced f (same bits)
-         else
-            amgk::jacobi_zero(s, slab_diag(v.A), f, l1 ? v.l1 : nullptr, D->o.smooth_weight, v.u, 0, v.n, 0);
-      } else if (k == 0 && allow_reuse && D->pre_ready) {
-         std::swap(v.u, v.u_alt);
-         D->pre_ready = false;
-      } else {
-         AmgProfLog::Scope pr(D->prof, 1, D->ctx->stream, D->o.profile && l == 0);
-         double *x = v.u, *out = v.u_alt;
-         AMG_TRY(split_A(D, v.A, x, [&](long long rb, long long re, long long) {
-            slab_jacobi(s, v.A, f, x, l1 ? v.l1 : nullptr, D->o.smooth_weight, out, rb, re);
-         }));
-         std::swap(v.u, v.u_alt);
-      }
-   }
-   return AMG_OK;
-}
+namespace {
 
 // coarse planes of level 1 whose fused residual + restriction reads only owned
 // u / f planes of level 0 (fine planes 2K - 1 .. 2K + 3 within the box)
@@ -292,11 +217,12 @@ void rr_interior(const amg_dist_hier *D, int &k0, int &k1)
    while (k1 > k0 && std::min(nz - 1, 2 * (k1 - 1) + 3) >= zb) k1--;
 }
 
+} // namespace
+
 // fused level-0 residual + restriction f_1 = R_0 (f - A_0 u) on the owned
 // coarse planes (dst: level 1's owned rows, or the allgather slot; dcz0 its
 // first coarse plane), overlapping u's exchange with the interior planes
-int s_res_restrict(amg_dist_hier *D, const double *f, double *u, double *dst, int dcz0,
-                   amgk::ZeroGuess zg = amgk::ZeroGuess())
+int amgd::s_res_restrict(amg_dist_hier *D, const double *f, double *u, double *dst, int dcz0, amgk::ZeroGuess zg)
 {
    amg_ctx *c = D->ctx;
    hipStream_t s = c->stream;
@@ -339,7 +265,7 @@ int s_res_restrict(amg_dist_hier *D, const double *f, double *u, double *dst, in
 
 // restricted residual at the first replicated level: every rank's owned
 // coarse rows (slot) allgathered and scattered into the full vector f_rep
-int s_gather(amg_dist_hier *D, hipStream_t s, double *slot, double *gath, double *full)
+int amgd::s_gather(amg_dist_hier *D, hipStream_t s, double *slot, double *gath, double *full)
 {
    amg_ctx *c = D->ctx;
    const int R = c->xport->nranks;
@@ -347,8 +273,6 @@ int s_gather(amg_dist_hier *D, hipStream_t s, double *slot, double *gath, double
    launch_scatter_blocks(s, gath, D->gath_blk, D->d_gcnt, D->d_gdsp, R, full);
    return AMG_OK;
 }
-
-} // namespace
 
 // ---------------------------------------------------------------------------
 // transfers (sync and async paths)
@@ -371,7 +295,7 @@ int amgd::slab_restrict(amg_dist_hier *D, hipStream_t s, int l, double *r, doubl
       }
       amgk::geo_restrict(s, v.g, v.d_geo_w, r - v.sg.off(), dst - coff, v.Ka, v.Kb, v.sg.e0(), cz0, zg);
    } else {
-      slab_spgemv(s, M, r, nullptr, amgk::gemv_mode(1.0, 0.0), dst, 0, M.nrows, nullptr);
+      dm_spgemv(s, M, r, nullptr, amgk::gemv_mode(1.0, 0.0), dst, 0, M.nrows, nullptr);
    }
    AMG_HIP(hipGetLastError());
    return AMG_OK;
@@ -390,176 +314,10 @@ int amgd::slab_prolong(amg_dist_hier *D, hipStream_t s, int l, double *x, double
       const int cz0 = from_rep ? 0 : D->lv[l + 1].sg.e0();
       amgk::geo_prolong(s, v.g, v.d_geo_w, x - coff, out - v.sg.off(), v.sg.za, v.sg.zb, v.sg.e0(), cz0);
    } else {
-      slab_spgemv(s, M, x, add ? out : nullptr, amgk::gemv_mode(1.0, add ? 1.0 : 0.0), out, 0, M.nrows, nullptr);
+      dm_spgemv(s, M, x, add ? out : nullptr, amgk::gemv_mode(1.0, add ? 1.0 : 0.0), out, 0, M.nrows, nullptr);
    }
    AMG_HIP(hipGetLastError());
    return AMG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// synchronous cycle
-// ---------------------------------------------------------------------------
-int amgd::slab_vcycle(amg_dist_hier *D, bool precond)
-{
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   const int L = D->L, Ld = D->Ld;
-   const amgk::Gemv res_mode = amgk::gemv_mode(-1.0, 1.0);
-   XchgFn xchg = [&](double *x, long long n, long long cP, const std::vector<int> &lo,
-                     const std::vector<int> &hi) { return slab_xchg(c, s, x, n, cP, lo, hi); };
-   const int R = c->xport->nranks;
-   double *slot = D->gath_buf ? D->gath_buf + (size_t)D->gath_blk * R : nullptr;
-   // a fold flag set by an earlier cycle that returned early (an error between
-   // the restriction and the level's smoothing) must not skip this cycle's sweep
-   for (auto &lv : D->lv) lv.zero_done = false;
-   for (int l = 0; l < Ld && l < L - 1; l++) {
-      DLevel &v = D->lv[l];
-      double *fl = (l == 0 && precond) ? D->r0 : v.f;
-      v.zero_flag = (l == 0 && !precond) ? 0 : 1;
-      AMG_TRY(s_smooth(D, l, fl, D->o.num_pre_smooth_sweeps, l == 0 && s_reuse(D)));
-      const bool to_rep = l + 1 == Ld;
-      double *dst = to_rep ? slot : D->lv[l + 1].f;
-      // a slab level l + 1 (not the coarsest) starts its pre-smoothing with the
-      // zero-guess sweep u = w f / a: a geometric restriction writes it with f
-      // (as the single-GPU V-cycle does, amg_solver.cpp vcycle)
-      amgk::ZeroGuess zg;
-      if (!to_rep && l + 1 < L - 1 && D->o.smoother == AMG_JACOBI && D->o.num_pre_smooth_sweeps >= 1 &&
-          zg_fold_on()) {
-         // the fold writes u_{l+1} / reads a_ii on the coarse rows both
-         // restrictions write: owned coarse planes [Ka, Kb) of level l + 1,
-         // indexed from its first owned row -- the level's own rows exactly
-         const DLevel &nx = D->lv[l + 1];
-         AMG_ARG(nx.sg.za == v.Ka && nx.sg.zb == v.Kb && (long long)nx.n == (long long)(v.Kb - v.Ka) * nx.sg.P &&
-                    nx.A.sro >= 0 && nx.A.sro + nx.n <= (long long)nx.A.A->nrows,
-                 "slab zero-guess fold: level %d owns planes [%d, %d) (%d rows, diag rows [%lld, +%d) of %d), "
-                 "the restriction writes [%d, %d)",
-                 l + 1, nx.sg.za, nx.sg.zb, nx.n, nx.A.sro, nx.n, nx.A.A->nrows, v.Ka, v.Kb);
-         zg.d = slab_diag(nx.A);
-         zg.w = D->o.smooth_weight;
-         zg.u = nx.u;
-         zg.hi = nx.n;
-         zg.err = c->d_err;
-      }
-      if (l == 0 && D->geo0) {
-         AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile);
-         // the right-hand side's ghost planes: f's were exchanged at the solve's
-         // start; the outer residual (preconditioner mode) changes every cycle
-         if (precond) AMG_TRY(slab_xchg(c, s, fl, v.n, v.sg.P, D->rr_flo, D->rr_fhi));
-         AMG_TRY(s_res_restrict(D, fl, v.u, dst, v.Ka, zg)); // dst: coarse plane Ka first
-         // level l + 1 is a slab level only below Ld (to_rep: the replicated
-         // tail, which has no DLevel -- D->lv holds Ld entries)
-         if (!to_rep) D->lv[l + 1].zero_done = zg.u != nullptr;
-      } else {
-         {
-            AmgProfLog::Scope pr(D->prof, 0, D->ctx->stream, D->o.profile && l == 0);
-            AMG_TRY(split_A(D, v.A, v.u, [&](long long rb, long long re, long long) {
-               slab_spgemv(s, v.A, v.u, fl, res_mode, v.r_fine, rb, re, nullptr);
-            }));
-         }
-         AmgProfLog::Scope pr(D->prof, 2, D->ctx->stream, D->o.profile && l == 0);
-         AMG_TRY(slab_restrict(D, s, l, v.r_fine, dst, xchg, v.geo ? zg : amgk::ZeroGuess()));
-         if (!to_rep) D->lv[l + 1].zero_done = v.geo && zg.u != nullptr;
-      }
-      if (to_rep) AMG_TRY(s_gather(D, s, slot, D->gath_buf, D->f_rep));
-   }
-   const double *u_rep = nullptr;
-   if (Ld < L) {
-      AMG_TRY(amg_hier_subcycle(D->coarse, s, D->f_rep, &u_rep));
-   } else {
-      DLevel &v = D->lv[L - 1];
-      const double *fl = (L == 1 && precond) ? D->r0 : v.f;
-      AMG_TRY(s_smooth(D, L - 1, fl, D->o.num_pre_smooth_sweeps + D->o.num_post_smooth_sweeps, false));
-   }
-   for (int l = std::min(Ld, L - 1) - 1; l >= 0; l--) {
-      DLevel &v = D->lv[l];
-      v.zero_flag = 0;
-      {
-         AmgProfLog::Scope pr(D->prof, 3, D->ctx->stream, D->o.profile && l == 0);
-         double *xc = (l + 1 < Ld) ? D->lv[l + 1].u : const_cast<double *>(u_rep);
-         AMG_TRY(slab_prolong(D, s, l, xc, v.u, true, xchg));
-      }
-      AMG_TRY(s_smooth(D, l, (l == 0 && precond) ? D->r0 : v.f, D->o.num_post_smooth_sweeps, false));
-   }
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
-}
-
-int amgd::slab_outer_residual(amg_dist_hier *D, int slot)
-{
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   DLevel &v = D->lv[0];
-   long long np = 0;
-   double *p;
-   AMG_TRY(amg_ctx_partials(c, (size_t)tiles(v.n) + 8, &p));
-   {
-      AmgProfLog::Scope pr(D->prof, 4, D->ctx->stream, D->o.profile);
-      if (s_reuse(D) && D->L > 1) {
-         const bool l1 = D->o.smoother == AMG_L1_JACOBI;
-         double *r0 = (D->o.reuse_outer_residual >= 2 && D->o.solver == AMG_MULT) ? nullptr : D->r0;
-         double *x = v.u, *un = v.u_alt;
-         AMG_TRY(split_A(D, v.A, x, [&](long long rb, long long re, long long poff) {
-            const DistMat &M = v.A;
-            amgk::residual_jacobi(s, M.A, v.f - M.sro, x - M.sco, l1 ? v.l1 - M.sro : nullptr,
-                                  D->o.smooth_weight, r0 ? r0 - M.sro : nullptr, un - M.sro,
-                                  (int)(M.sro + rb), (int)(M.sro + re), p + poff);
-         }, &np));
-         D->pre_ready = true;
-      } else {
-         double *x = dist_iterate(D);
-         AMG_TRY(split_A(D, v.A, x, [&](long long rb, long long re, long long poff) {
-            slab_spgemv(s, v.A, x, v.f, amgk::gemv_mode(-1.0, 1.0), D->r0, rb, re, p + poff);
-         }, &np));
-         D->pre_ready = false;
-      }
-   }
-   double *sum = D->d_hist + slot;
-   amgk::reduce_partials(s, p, (int)np, sum, 0, c->d_scalars + 4096);
-   AMG_TRY(xp_allreduce(c, s, sum, 1));
-   launch_sqrt(s, sum, sum);
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
-}
-
-int amgd::slab_solve_begin(amg_dist_hier *D, const double *f_local)
-{
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   for (auto &v : D->lv) {
-      for (double *p : {v.f, v.u, v.u_alt, v.r_fine})
-         amgk::vset(s, p - v.sg.off(), 0.0, 0, (int)v.sg.ext_rows());
-      v.zero_flag = 0;
-   }
-   DLevel &v0 = D->lv[0];
-   amgk::vset(s, D->r0 - v0.sg.off(), 0.0, 0, (int)v0.sg.ext_rows());
-   AMG_TRY(h2d(s, v0.f, f_local, (size_t)v0.n * sizeof(double)));
-   if (D->geo0) AMG_TRY(slab_xchg(c, s, v0.f, v0.n, v0.sg.P, D->rr_flo, D->rr_fhi));
-   if (D->coarse) AMG_TRY(amg_hier_reset(D->coarse));
-   if (D->x_acc) {
-      amgk::vset(s, D->x_acc - v0.sg.off(), 0.0, 0, (int)v0.sg.ext_rows());
-      amgk::vset(s, D->d_acc, 0.0, 0, std::max(1, v0.n));
-   }
-   D->acc.reset(D->o);
-   D->iter = 0;
-   AMG_TRY(slab_outer_residual(D, 0));
-   AMG_TRY(d2h(s, c->h_pinned, D->d_hist, sizeof(double)));
-   D->r0norm = c->h_pinned[0];
-   D->have_state = true;
-   return AMG_OK;
-}
-
-int amgd::slab_fine_spmv(amg_dist_hier *D, int reps, double *ms)
-{
-   amg_ctx *c = D->ctx;
-   DLevel &v = D->lv[0];
-   hipStream_t s = c->stream;
-   const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   auto spmv = [&] {
-      return split_A(D, v.A, v.u, [&](long long rb, long long re, long long) {
-         slab_spgemv(s, v.A, v.u, nullptr, mv, v.r_fine, rb, re, nullptr);
-      });
-   };
-   return amg_timed_reps(s, reps, spmv, ms);
 }
 
 // ---------------------------------------------------------------------------

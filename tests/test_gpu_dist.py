@@ -117,12 +117,16 @@ def test_dist_matches_single_gpu(amg, ctx, dims, interp, nranks, rep, extra):
     gen.free()
 
 
-def test_dist_restart_is_fresh(amg, ctx):
-    """A second solve on the same distributed hierarchy starts from zero on every
-    level (replicated coarsest included): identical to the first."""
-    gen = amg.Gen(24)
-    opts = amg.default_opts(num_cycles=4, tol=0.0)
-    f = amg.rhs_rand(0, 24 ** 3)
+def restart_ranks(amg, form, opts, cycles):
+    """Two solves of `cycles` cycles on one 2-rank hierarchy of the given form;
+    per rank: (first iterate, second iterate, slab_info's fused flag, the
+    context's device range-check flags)."""
+    slab = form == "slab"
+    # slab: the smallest box whose level 0 runs the fused residual + restriction
+    # (nx >= 64), so that solve-begin's exchange of f's ghost planes is exercised
+    dims = (64, 64, 32) if slab else (24, 24, 24)
+    gen = amg.Gen(*dims)
+    f = amg.rhs_rand(0, dims[0] * dims[1] * dims[2])
     hub = amg.dist.ThreadMailbox(2)
 
     def rank(r):
@@ -130,20 +134,52 @@ def test_dist_restart_is_fresh(amg, ctx):
         tr = amg.dist.HostTransport(hub, r)
         amg.dist.init_host(c, 2, r, tr)
         amg.dist.set_replicate_rows(c, 4096)
-        D = amg.dist.DistHier(c, gen, opts)
+        D = amg.dist.DistHier(c, gen, opts, slab=slab)
+        fused = D.slab_info()[2]
         outs = []
         for _ in range(2):
             D.solve_start(f[D.row0:D.row0 + D.n0])
-            D.iterate(4)
+            D.iterate(cycles)
             outs.append(D.get_u())
         D.free()
+        errs = c.device_errors()
         amg.dist.finalize(c)
         c.close()
-        return outs
+        if tr.error is not None:
+            raise tr.error
+        return outs[0], outs[1], fused, errs
 
-    for a, b in run_ranks(2, rank):
-        assert_bitwise(a, b, "restart")
+    res = run_ranks(2, rank)
     gen.free()
+    return res
+
+
+def check_restart(res, form, what):
+    for a, b, fused, errs in res:
+        assert_bitwise(b, a, what)
+        assert np.all(np.isfinite(a)) and np.any(a != 0.0)
+        assert fused == (1 if form == "slab" else 0), (form, fused)
+        assert errs == 0, f"device range-check flags {errs:#x}"
+
+
+@pytest.mark.parametrize("form", ["rows", "slab"])
+def test_dist_restart_is_fresh(amg, form):
+    """A second solve on the same distributed hierarchy starts from zero on every
+    level (replicated coarsest included): identical to the first.  The slab
+    case runs the fused level 0, whose f ghost planes solve-begin exchanges."""
+    opts = amg.default_opts(num_cycles=4, tol=0.0)
+    check_restart(restart_ranks(amg, form, opts, 4), form, "restart")
+
+
+@pytest.mark.parametrize("form", ["rows", "slab"])
+def test_dist_restart_is_fresh_accelerated(amg, form):
+    """Accelerated MULT (DMEM_Mult with the Richardson update): a second solve
+    also starts the iterate x, the update direction d and the ChebyUpdate
+    recurrence afresh -- bit-identical to the first."""
+    mu, delta = cheby_scalars(0.5, 4.0)
+    opts = amg.default_opts(num_cycles=3, tol=0.0, smooth_weight=0.8, accel_type=amg.AMG_RICHARD_ACCEL,
+                            cheby_mu=mu, cheby_delta=delta)
+    check_restart(restart_ranks(amg, form, opts, 3), form, "accelerated restart")
 
 
 def test_dist_allreduce(amg):
