@@ -173,7 +173,8 @@ class Context:
     def set_fuse_outer(self, mode):
         """level 0's last post sweep + the outer residual as one march (0 off, 1 on, 2 on with u'
         stored only at the end of an iterate batch, 3 the two sweeps slab by slab over z through the
-        Infinity Cache, u' stored as in 2; bit-identical)"""
+        Infinity Cache, u' stored as in 2, 4 one register march that shares every load between
+        the two sweeps, u' stored as in 2 (the default); bit-identical)"""
         check(lib.amg_set_fuse_outer(self.h, int(mode)))
 
     def set_outer_slab(self, planes):

@@ -166,7 +166,7 @@ extern "C" int amg_init(amg_ctx **out, int device, int nstreams)
    if (const char *v = std::getenv("AMG_LONG_FORM")) c->long_form = std::max(0, std::min(2, std::atoi(v)));
    if (const char *v = std::getenv("AMG_LONG_XCD")) c->long_xcd = std::atoi(v) != 0;
    if (const char *v = std::getenv("AMG_OUTER_SLAB")) c->outer_slab = std::max(1, std::atoi(v));
-   if (const char *v = std::getenv("AMG_FUSE_OUTER")) c->fuse_outer = std::max(0, std::min(3, std::atoi(v)));
+   if (const char *v = std::getenv("AMG_FUSE_OUTER")) c->fuse_outer = std::max(0, std::min(4, std::atoi(v)));
    if (const char *v = std::getenv("AMG_FUSE_XFP_SLAB")) c->fuse_xfp_slab = std::atoi(v) != 0;
    if (const char *v = std::getenv("AMG_FUSE_PROLONG")) c->fuse_prolong = std::max(0, std::min(7, std::atoi(v)));
    if (const char *v = std::getenv("AMG_JGS_SMALL")) c->jgs_small = std::max(0, std::min(2, std::atoi(v)));
@@ -965,7 +965,7 @@ extern "C" int amg_set_march_lines_gemv(amg_ctx *c, int lines)
 
 extern "C" int amg_set_fuse_outer(amg_ctx *c, int mode)
 {
-   AMG_ARG(c && mode >= 0 && mode <= 3, "amg_set_fuse_outer: mode 0, 1, 2 or 3");
+   AMG_ARG(c && mode >= 0 && mode <= 4, "amg_set_fuse_outer: mode 0, 1, 2, 3 or 4");
    c->knob_gen++; // cached hipGraphs were captured with the old setting
    c->fuse_outer = mode;
    return AMG_OK;

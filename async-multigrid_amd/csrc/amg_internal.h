@@ -118,9 +118,10 @@ struct amg_ctx {
    int fuse_xfp_slab = 0;  // ... and the slab async solve's fused prolongation + atomic (AMG_FUSE_XFP_SLAB)
    int fuse_prolong = 0;   // prolongation fused into the first post sweep (measured slower: off)
    int bsr3_xs = 1;        // 3x3 block kernel: one x load per lane, shared over the triplet (AMG_BSR3_XS)
-   int fuse_outer = 0;     // level 0's last post sweep + the outer residual as one march (AMG_FUSE_OUTER;
+   int fuse_outer = 4;     // level 0's last post sweep + the outer residual as one march (AMG_FUSE_OUTER;
                            // 1: u' stored every step, 2: only at the end of an iterate batch;
-                           // 3: the two sweeps slab by slab over z through the Infinity Cache, u' as in 2)
+                           // 3: the two sweeps slab by slab over z through the Infinity Cache, u' as in 2;
+                           // 4: the register march mz_two_sweep_kernel, u' as in 2)
    int outer_slab = 32;    // planes per z-slab of fuse_outer 3 (AMG_OUTER_SLAB): a slab's u, f and u'
                            // (3 x 32 x 2 MB at 512^2 planes) stay in the 256 MiB Infinity Cache
    int rr_lines = 1;       // coarse lines per lane of the fused residual + restriction (1 or 2)

@@ -3959,6 +3959,223 @@ mz_sweep_outer_kernel(
    }
 }
 
+// ---------------------------------------------------------------------------
+// The same fused pair as a register march (mz_two_sweep_kernel, fuse_outer 4).
+// mz_sweep_outer_kernel saves the HBM round trip of u' but issues as many
+// vector loads per plane as the two separate marches (its halo teams load
+// their own u, f and +-S lines), and the level-0 marches are bound by memory
+// requests.  Here one 256-lane workgroup owns NL adjacent lines (lane t: rows
+// 2t, 2t + 1 of each, as in csr_mz_kernel) and keeps everything both sweeps
+// share in registers:
+//   * sweep 1 (the post sweep) runs on the NL + 2 lines y0-1 .. y0+NL, one
+//     plane ahead of sweep 2: u of planes k-1, k, k+1 of those lines stays in
+//     registers (plane k + 2 is prefetched), so the +-S operands of all but
+//     the two outermost lines and every +-P operand are register reads; per
+//     plane only the two halo lines y0-2, y0+NL+1, f and the pattern byte of
+//     the NL + 2 lines are loaded;
+//   * sweep 2 (the outer residual + next first sweep) runs at plane k - 1 on
+//     the NL own lines entirely from registers: u' of plane k - 1 on all
+//     NL + 2 lines (+-S), of planes k - 2 and k on the own lines (+-P), f and
+//     the pattern byte kept from the step before;
+//   * +-1 come from the neighbour lanes; the wave-edge operands of both sweeps
+//     (u of plane k + 1, u' of plane k) pass between the workgroup's four
+//     waves through two small double-buffered LDS arrays, written one plane
+//     step before they are read: one barrier per plane step orders both;
+//   * a chunk runs sweep 1 over planes k0-1 .. k1 and sweep 2 over k0 .. k1-1.
+// Per two output lines and plane: 6 u loads, 4 f loads, 4 pattern bytes and 2
+// stores (more with r and / or u'), against 20 loads, 4 two-lane edge loads
+// and 4 stores of the two marches.  A halo line or plane of u' that the neighbouring workgroup owns
+// goes through the same instructions on the same operands there, so it is the
+// same value; lines and planes outside the box are clamped to a valid address
+// and their u' is never a used operand.  u', u'', r and every partial are
+// bit-identical to the two launches.  Needs S = 512 and NL | P / S.
+// ---------------------------------------------------------------------------
+constexpr int AMG_MZR_NL = 2;
+
+template <int NL, bool STORE_U, bool STORE_R>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void mz_two_sweep_kernel(
+   const unsigned char *__restrict__ ppat, const unsigned long long *__restrict__ mmask_g, int np, MpSten Sv,
+   const double *__restrict__ f, const double *__restrict__ u, double *__restrict__ u1out,
+   double *__restrict__ rout, double *__restrict__ unext, double omega, int P, int nz, int zc, int npb, int xcd,
+   double *__restrict__ partials, double dq, double rq)
+{
+   constexpr int NS = NL + 2, S = 512;
+   __shared__ unsigned long long mtab[256];
+   // wave-edge values [buffer][line][wave]: {lane 0's .x, lane 63's .y}
+   __shared__ double ue[2][NS][4][2];
+   __shared__ double we[2][NL][4][2];
+   __shared__ double red[AMG_MZ_MAXZC * NL * 8];
+   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+   if (tid < np) mtab[tid] = mmask_g[tid];
+   const int G = (int)gridDim.x;
+   int lg = (int)blockIdx.x;
+   if (xcd && (G & 7) == 0) lg = (lg & 7) * (G >> 3) + (lg >> 3);
+   const int pblk = lg % npb, chunk = lg / npb;
+   const int k0 = chunk * zc, k1 = min(k0 + zc, nz);
+   const int ny = P / S, y0 = pblk * NL;
+   // in-plane offsets of lines y0-1 .. y0+NL and of the two halo lines (lines
+   // past the box: a valid line, never a used operand); they and the plane
+   // offsets are workgroup-uniform, so every address is a scalar base plus the
+   // lane's one pair offset
+   auto lofs = [&](int y) { return (unsigned)((y < 0 ? 0 : (y >= ny ? ny - 1 : y)) * S); };
+   unsigned lof[NS];
+#pragma unroll
+   for (int j = 0; j < NS; j++) lof[j] = lofs(y0 - 1 + j);
+   const unsigned lofm = lofs(y0 - 2), lofp = lofs(y0 + NL + 1);
+   const unsigned lo = 2u * (unsigned)tid;
+   const double a0 = Sv.val[0];
+   const v2d a2{a0, a0};
+   auto ldp = [&](int k, int j) {
+      return (k >= 0 && k < nz) ? ld2u(u + ((size_t)k * P + lof[j]), lo) : v2d{0.0, 0.0};
+   };
+   // the pair's +-1 operands that lie in the neighbouring waves (a line's two
+   // ends: none, those entries are unused)
+   auto edge = [&](const double (&e)[4][2]) {
+      double v = 0.0;
+      if (lane == 0 && wv > 0) v = e[wv - 1][1];
+      if (lane == 63 && wv < 3) v = e[wv + 1][0];
+      return v;
+   };
+   // u of planes k-1, k, k+1 (sweep 1 at plane k)
+   v2d um[NS], uc[NS], uq[NS];
+#pragma unroll
+   for (int j = 0; j < NS; j++) {
+      um[j] = ldp(k0 - 2, j);
+      uc[j] = ldp(k0 - 1, j);
+      uq[j] = ldp(k0, j);
+      if (lane == 0) ue[(k0 - 1) & 1][j][wv][0] = uc[j].x;
+      if (lane == 63) ue[(k0 - 1) & 1][j][wv][1] = uc[j].y;
+   }
+   // sweep-2 state: u' of plane k-2 (own lines) and k-1 (all lines); f and the
+   // pattern of plane k-1 (own lines)
+   v2d wm[NL], wc[NS], fm[NL];
+   int pidm[NL];
+#pragma unroll
+   for (int j = 0; j < NS; j++) wc[j] = v2d{0.0, 0.0};
+#pragma unroll
+   for (int i = 0; i < NL; i++) {
+      wm[i] = fm[i] = v2d{0.0, 0.0};
+      pidm[i] = 0;
+   }
+   __syncthreads();
+   for (int k = k0 - 1; k <= k1; k++) {
+      const bool s1 = k >= 0 && k < nz; // workgroup-uniform
+      const size_t base = (size_t)(k < 0 ? 0 : (k >= nz ? nz - 1 : k)) * P;
+      // this plane's operands
+      const v2d ym = ld2u(u + (base + lofm), lo), yp = ld2u(u + (base + lofp), lo);
+      v2d fv[NS], un[NS];
+      int pid[NS];
+#pragma unroll
+      for (int j = 0; j < NS; j++) {
+         fv[j] = ld2u(f + (base + lof[j]), lo);
+         pid[j] = (ppat + ((base + lof[j]) >> 1))[tid];
+      }
+      // the next step's wave edges of u (plane k + 1)
+#pragma unroll
+      for (int j = 0; j < NS; j++) {
+         if (lane == 0) ue[(k + 1) & 1][j][wv][0] = uq[j].x;
+         if (lane == 63) ue[(k + 1) & 1][j][wv][1] = uq[j].y;
+      }
+      // ---- sweep 1 at plane k: u' = u + w (f - A u) ./ a (EpiJacobi) ----
+      v2d w1[NS];
+#pragma unroll
+      for (int j = 0; j < NS; j++) {
+         w1[j] = v2d{0.0, 0.0};
+         if (s1) {
+            const double e = edge(ue[k & 1][j]);
+            double lft = __shfl_up(uc[j].y, 1, 64);
+            double rgt = __shfl_down(uc[j].x, 1, 64);
+            if (lane == 0) lft = e;
+            if (lane == 63) rgt = e;
+            const unsigned long long mk = mtab[pid[j]];
+            v2d xv[7];
+            xv[0] = uc[j];
+            xv[1] = um[j];
+            xv[2] = j == 0 ? ym : uc[j == 0 ? 0 : j - 1];
+            xv[3] = v2d{lft, uc[j].x};
+            xv[4] = v2d{uc[j].y, rgt};
+            xv[5] = j == NS - 1 ? yp : uc[j == NS - 1 ? 0 : j + 1];
+            xv[6] = uq[j];
+            const v2d acc = mz_acc7<1, true>(fv[j], xv, mk, Sv, nullptr);
+            const v2d q = jac_div2(v2d{omega * acc.x, omega * acc.y}, a2, dq, rq);
+            w1[j] = v2d{(a0 != 0.0) ? uc[j].x + q.x : uc[j].x, (a0 != 0.0) ? uc[j].y + q.y : uc[j].y};
+            if (j >= 1 && j <= NL) {
+               if (STORE_U && k >= k0 && k < k1)
+                  *reinterpret_cast<v2du *>(u1out + ((size_t)k * P + lof[j]) + lo) = w1[j];
+               // the next step's wave edges of u' (plane k)
+               if (lane == 0) we[k & 1][j - 1][wv][0] = w1[j].x;
+               if (lane == 63) we[k & 1][j - 1][wv][1] = w1[j].y;
+            }
+         }
+      }
+      // u of plane k + 2 (sweep 1 at plane k + 1) takes the registers plane
+      // k - 1 leaves and is in flight across sweep 2 and the barrier
+#pragma unroll
+      for (int j = 0; j < NS; j++) un[j] = k < k1 ? ldp(k + 2, j) : v2d{0.0, 0.0};
+      // ---- sweep 2 at plane k - 1 (own lines): r = f - A u', u'' = u' + w r ./ a ----
+      const int km = k - 1;
+      if (km >= k0) {
+#pragma unroll
+         for (int i = 0; i < NL; i++) {
+            const int j = i + 1;
+            const double e = edge(we[km & 1][i]);
+            double lft = __shfl_up(wc[j].y, 1, 64);
+            double rgt = __shfl_down(wc[j].x, 1, 64);
+            if (lane == 0) lft = e;
+            if (lane == 63) rgt = e;
+            const unsigned long long mk = mtab[pidm[i]];
+            v2d xv[7];
+            xv[0] = wc[j];
+            xv[1] = wm[i];
+            xv[2] = wc[j - 1];
+            xv[3] = v2d{lft, wc[j].x};
+            xv[4] = v2d{wc[j].y, rgt};
+            xv[5] = wc[j + 1];
+            xv[6] = w1[j];
+            const v2d res = mz_acc7<1, true>(fm[i], xv, mk, Sv, nullptr);
+            const size_t row = (size_t)km * P + lof[j];
+            if (STORE_R) *reinterpret_cast<v2du *>(rout + row + lo) = res;
+            const v2d q = jac_div2(v2d{omega * res.x, omega * res.y}, a2, dq, rq);
+            const v2d v{(a0 != 0.0) ? wc[j].x + q.x : wc[j].x, (a0 != 0.0) ? wc[j].y + q.y : wc[j].y};
+            *reinterpret_cast<v2du *>(unext + row + lo) = v;
+            if (partials) {
+               // csr_mz_kernel's 64-row group sums
+               double a = res.x * res.x, b = res.y * res.y;
+#pragma unroll
+               for (int off = 16; off > 0; off >>= 1) {
+                  a += __shfl_down(a, off, 32);
+                  b += __shfl_down(b, off, 32);
+               }
+               if ((tid & 31) == 0) red[((km - k0) * NL + i) * 8 + (tid >> 5)] = a + b;
+            }
+         }
+      }
+      // the edge arrays' RAW (written this step, read the next) and WAR (read
+      // this step, overwritten the next) hazards both fall on this barrier
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < NL; i++) {
+         wm[i] = wc[i + 1];
+         fm[i] = fv[i + 1];
+         pidm[i] = pid[i + 1];
+      }
+#pragma unroll
+      for (int j = 0; j < NS; j++) {
+         wc[j] = w1[j];
+         um[j] = uc[j];
+         uc[j] = uq[j];
+         uq[j] = un[j];
+      }
+   }
+   if (partials) {
+      for (int w = tid; w < 2 * NL * (k1 - k0); w += 256) {
+         const int it = w / (2 * NL), i = (w >> 1) % NL, h = w & 1;
+         const double *g = red + (it * NL + i) * 8 + 4 * h;
+         partials[((long long)(k0 + it) * P + (long long)(y0 + i) * S) / 256 + h] = ((g[0] + g[1]) + g[2]) + g[3];
+      }
+   }
+}
+
 // can level 0's last post-sweep and the outer residual run as one march?
 bool mz_sweep_outer_ok(const amg_mat *A)
 {
@@ -3975,6 +4192,22 @@ void mz_sweep_outer(hipStream_t s, const amg_mat *A, const double *f, const doub
 {
    const MpSten Sv = mp_sten(A);
    const int P = A->mz_P, nz = A->nrows / P;
+   if (A->ctx->fuse_outer == 4) {
+      // the register march: long chunks (each recomputes two planes of sweep
+      // 1), a whole number of rounds of the launched instantiation's occupancy
+      double dq = 0.0, rq = 0.0;
+      if (!fast_div_of(A, &dq, &rq)) dq = rq = 0.0;
+      const int npb = P / (512 * AMG_MZR_NL);
+      pick_bool(u1out != nullptr, [&](auto store) {
+         pick_bool(rout != nullptr, [&](auto res) {
+            auto *fn = mz_two_sweep_kernel<AMG_MZR_NL, decltype(store)::value, decltype(res)::value>;
+            const int zc = occ_chunk(A, nz, npb, -1, (const void *)fn), nch = (nz + zc - 1) / zc;
+            fn<<<npb * nch, 256, 0, s>>>(A->ppat, A->mpmask, A->pp_n, Sv, f, u, u1out, rout, unext, omega, P, nz, zc,
+                                         npb, A->ctx->mz_xcd, partials, dq, rq);
+         });
+      });
+      return;
+   }
    const int npb = P / (512 * AMG_MZF_NL);
    int zc = std::max(1, std::min(A->ctx->mz_zc, AMG_MZ_MAXZC));
    if (A->ctx->mz_zc_auto) zc = (int)std::max(1LL, std::min((long long)zc, (long long)nz * npb / 1024));

@@ -437,8 +437,11 @@ int amg_hier_fused_prolong(const amg_hier *H);
  * registers); 3: the two sweeps as ordinary marches slab by slab over z
  * (amg_set_outer_slab planes each), the second reading u' and f back from the
  * Infinity Cache, u' written as in mode 2 (any plane-marched A0 whose planes
- * are multiples of 256 rows, Jacobi or L1 Jacobi); bit-identical to the two
- * marches.  AMG_FUSE_OUTER sets it too. */
+ * are multiples of 256 rows, Jacobi or L1 Jacobi); 4: one register march, a
+ * 256-lane workgroup holding two adjacent lines plus their two halo lines of
+ * u and u' in registers so that both sweeps share every load, u' written as
+ * in mode 2 (same operators as modes 1 and 2); bit-identical to the two
+ * marches.  The default is 4; AMG_FUSE_OUTER sets it too. */
 int amg_set_fuse_outer(amg_ctx *ctx, int mode);
 /* planes per z-slab of fuse_outer mode 3 (default 32; env AMG_OUTER_SLAB) */
 int amg_set_outer_slab(amg_ctx *ctx, int planes);

@@ -16,6 +16,8 @@ KERNELS = {
     # name in bench.fine_kernels: (kernel pattern, algorithmic bytes per launch as f(n))
     "outer_residual_sweep": (r"csr_mz_kernel<1, true, amgk::EpiResJacobi", lambda r: (r + 1) // 2 + 24 * r),
     "post_sweep": (r"csr_mz_kernel<1, true, amgk::EpiJacobi,", lambda r: (r + 1) // 2 + 24 * r),
+    # fuse_outer 4, the launches that do not store u' (every step of a batch but its last)
+    "post_sweep_outer_residual": (r"mz_two_sweep_kernel<\d+, false", lambda r: (r + 1) // 2 + 24 * r),
     # + level 1's zero-guess sweep folded in: f_1, u_1 written, a_1 read (r / 8 rows each)
     "residual_restrict": (r"mz_res_restrict_kernel", lambda r: (r + 1) // 2 + 16 * r + 3 * r),
     "prolong_sweep": (r"mz_prolong_sweep", lambda r: (r + 1) // 2 + 24 * r + r),

@@ -1,12 +1,14 @@
 """Per-step kernel timeline of a rocprofv3 kernel trace of bench.py: the
-kernels between two consecutive outer-residual launches (one step), with
+kernels between two consecutive outer-residual launches (one step; the fused
+post sweep + outer residual marches count as such), with
 their durations, the step's wall span and its busy time."""
 import csv
 import re
 import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "EpiResJacobi" in r["Kernel_Name"]]
+OUTER = ("EpiResJacobi", "mz_two_sweep_kernel", "mz_sweep_outer_kernel")
+idx = [i for i, r in enumerate(rows) if any(k in r["Kernel_Name"] for k in OUTER)]
 a, b = idx[-3], idx[-2]
 seg = rows[a:b]
 wall = (int(rows[b]["Start_Timestamp"]) - int(rows[a]["Start_Timestamp"])) / 1e6
