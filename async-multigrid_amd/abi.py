@@ -217,6 +217,14 @@ PROTOTYPES = {
     "amg_dist_solve_iterate": (_i, [_p, _i]),
     "amg_dist_solve_resnorm": (_i, [_p, _dp]),
     "amg_dist_get_u": (_i, [_p, _dp]),
+    "amg_dist_precond_apply": (_i, [_p, _dp, _dp]),
+    "amg_dist_pcg_start": (_i, [_p, _dp, _dp, _dp]),
+    "amg_dist_pcg_iterate": (_i, [_p, _i]),
+    "amg_dist_pcg_resnorm": (_i, [_p, _dp]),
+    "amg_dist_pcg_get_x": (_i, [_p, _dp]),
+    "amg_dist_pcg_get_r": (_i, [_p, _dp]),
+    "amg_dist_pcg_scalars": (_i, [_p, _dp, _dp, _dp, _i, _ip]),
+    "amg_dist_pcg_solve": (_i, [_p, _dp, _dp, _dp, _ip]),
     "amg_dist_hier_free": (_i, [_p]),
     "amg_dist_profile_read": (_i, [_p, _dp, _llp, _i]),
     "amg_dist_fine_spmv": (_i, [_p, _i, _dp]),

@@ -1081,8 +1081,9 @@ int dist_smooth(amg_dist_hier *D, int l, const double *f, int sweeps, bool allow
 // SMEM_Sync_Parfor_Vcycle on the distributed levels.  precond: the cycle runs
 // on the outer residual r0 from a zero level-0 guess (precond_flag, the form
 // DMEM_MultCycle takes with precond_zero_init_guess = 1) and leaves the
-// correction in lv[0].u
-int dist_vcycle(amg_dist_hier *D, bool precond)
+// correction in lv[0].u.  zero0_done: lv[0].u already holds level 0's
+// zero-guess pre-sweep on r0 (the PCG residual update wrote it: same bits)
+int dist_vcycle(amg_dist_hier *D, bool precond, bool zero0_done = false)
 {
    amg_ctx *c = D->ctx;
    hipStream_t s = c->stream;
@@ -1091,6 +1092,7 @@ int dist_vcycle(amg_dist_hier *D, bool precond)
    // a fold flag set by an earlier cycle that returned early (an error between
    // the restriction and the level's smoothing) must not skip this cycle's sweep
    for (auto &lv : D->lv) lv.zero_done = false;
+   D->lv[0].zero_done = zero0_done;
    for (int l = 0; l < Ld && l < L - 1; l++) {
       DLevel &v = D->lv[l];
       double *fl = (l == 0 && precond) ? D->r0 : v.f;
@@ -1250,6 +1252,7 @@ int amgd::dist_solve_begin(amg_dist_hier *D, const double *f_local)
    }
    D->acc.reset(D->o);
    D->iter = 0;
+   D->pcg.on = false; // r0 and lv[0].u (PCG's r and z) belong to the new solve
    AMG_TRY(dist_outer_residual(D, 0));
    AMG_TRY(d2h(s, c->h_pinned, D->d_hist, sizeof(double)));
    D->r0norm = c->h_pinned[0];
@@ -1316,6 +1319,237 @@ extern "C" int amg_dist_get_u(amg_dist_hier *D, double *u_local)
    AMG_ARG(D && u_local, "amg_dist_get_u: null argument");
    AMG_HIP(hipStreamSynchronize(D->ctx->stream));
    AMG_TRY(d2h(D->ctx->stream, u_local, dist_iterate(D), (size_t)D->lv[0].n * sizeof(double)));
+   return AMG_OK;
+}
+
+// ---- preconditioned CG across ranks (-hypre_pcg: DMEM_Main.cpp:363-364, 788-804; --
+// DMEM_Setup.cpp:129-165 installs DMEM_MultCycle from a zero guess as HYPRE PCG's
+// preconditioner on the rank-partitioned A_fine) --------------------------------------
+// amg_pcg_*'s recurrence (amg_solver.cpp) on this rank's rows: q = A p is the
+// distributed product, M^-1 one dist_vcycle in preconditioner mode, and each dot
+// product is this rank's sum in amg_vec_dot's order, all-gathered and added in
+// rank order by the kernel that forms the quotient (amg_pcg.hip).  Two gathers
+// per iteration: p.q, then (r.r, r.z) together after the preconditioner.
+namespace {
+
+int dpcg_check(const amg_dist_hier *D, const char *who)
+{
+   AMG_ARG(D->o.solver == AMG_MULT,
+           "%s: solver %d cannot precondition CG across ranks (MULT hierarchies only: the only "
+           "synchronous distributed cycle)", who, D->o.solver);
+   AMG_ARG(D->o.accel_type == AMG_NO_ACCEL, "%s: accel_type %d does not apply to PCG (AMG_NO_ACCEL only)", who,
+           D->o.accel_type);
+   return AMG_OK;
+}
+
+// can the residual update write level 0's zero-guess pre-sweep?  (pcg_fuse_zero
+// of one GPU: the cycle's level 0 starts with jacobi_zero on r0)
+bool dpcg_fuse_zero(const amg_dist_hier *D) { return D->L > 1 && D->o.num_pre_smooth_sweeps >= 1; }
+
+// lv[0].u = M^-1 r0 (r0 is left as it is) from a zero state on every level.
+// zero0_done: lv[0].u already holds the cycle's first level-0 sweep on r0
+int dpcg_precond(amg_dist_hier *D, bool zero0_done = false)
+{
+   hipStream_t s = D->ctx->stream;
+   D->pre_ready = false;
+   D->have_state = false; // the stationary solve's u and r0 are overwritten
+   // the owned rows (ghosts are exchanged before they are read).  Below level 0
+   // the zero-guess sweep writes u too, but not where a_ii = 0 nor with no pre-sweep
+   for (int l = zero0_done ? 1 : 0; l < D->Ld; l++) amgk::vset(s, D->lv[l].u, 0.0, 0, D->lv[l].n);
+   D->lv[0].zero_flag = 0; // a one-level cycle smooths from the cleared u
+   if (D->coarse) AMG_TRY(amg_hier_zero_iterates(D->coarse));
+   return dist_vcycle(D, true, zero0_done);
+}
+
+int dpcg_alloc(amg_dist_hier *D)
+{
+   amg_dist_hier::Pcg &g = D->pcg;
+   if (!g.x) AMG_TRY(lvec(D, 0, &g.x));
+   if (!g.p) AMG_TRY(lvec(D, 0, &g.p));
+   if (!g.q) AMG_TRY(lvec(D, 0, &g.q));
+   if (!g.sc) AMG_TRY(dvec(D, amgk::PCG_NSCALARS, &g.sc));
+   if (!g.part_rr) AMG_TRY(dvec(D, 1024, &g.part_rr));
+   if (!g.part_dot) AMG_TRY(dvec(D, 1024, &g.part_dot));
+   if (!g.ring) AMG_TRY(dvec(D, 3 * (size_t)amgk::PCG_RING, &g.ring));
+   if (!g.slot) AMG_TRY(dvec(D, 2, &g.slot));
+   if (!g.gath) AMG_TRY(dvec(D, 2 * (size_t)D->ctx->xport->nranks, &g.gath));
+   return AMG_OK;
+}
+
+int dpcg_hist_slot(const amg_dist_hier *D) { return D->pcg.iter % (D->hist_cap - 1); }
+
+// rho (and beta) from r0 . lv[0].u and ||r|| into the history from the r.r
+// partials: one gather of this rank's two sums
+int dpcg_finish_dots(amg_dist_hier *D, int first)
+{
+   amg_dist_hier::Pcg &g = D->pcg;
+   amg_ctx *c = D->ctx;
+   hipStream_t s = c->stream;
+   int np = 0;
+   amgk::dot_partials(s, D->r0, D->lv[0].u, D->lv[0].n, g.part_dot, &np); // the r.r partials' grid too
+   amgk::pcg_rank_sum(s, g.part_rr, g.part_dot, np, g.slot);
+   AMG_TRY(xp_allgather(c, s, g.slot, g.gath, 2 * sizeof(double)));
+   const int ring = first ? 0 : (g.iter - 1) % amgk::PCG_RING;
+   amgk::pcg_beta_ranks(s, g.gath, c->xport->nranks, g.sc, D->d_hist + dpcg_hist_slot(D),
+                        g.ring + amgk::PCG_RING + ring, g.ring + 2 * amgk::PCG_RING + ring, first);
+   return AMG_OK;
+}
+
+} // namespace
+
+extern "C" int amg_dist_precond_apply(amg_dist_hier *D, const double *r_local, double *z_local)
+{
+   AMG_ARG(D && r_local && z_local, "amg_dist_precond_apply: null argument");
+   AMG_TRY(dpcg_check(D, "amg_dist_precond_apply"));
+   hipStream_t s = D->ctx->stream;
+   DLevel &v = D->lv[0];
+   D->pcg.on = false; // a running PCG's r and z are overwritten
+   AMG_TRY(h2d(s, D->r0, r_local, (size_t)v.n * sizeof(double)));
+   AMG_TRY(dpcg_precond(D));
+   AMG_TRY(d2h(s, z_local, v.u, (size_t)v.n * sizeof(double)));
+   return AMG_OK;
+}
+
+extern "C" int amg_dist_pcg_start(amg_dist_hier *D, const double *f_local, const double *x0_local, double *r0norm)
+{
+   AMG_ARG(D && f_local, "amg_dist_pcg_start: null argument");
+   AMG_TRY(dpcg_check(D, "amg_dist_pcg_start")); // before any collective: a refused call leaves no peer waiting
+   AMG_TRY(dpcg_alloc(D));
+   amg_ctx *c = D->ctx;
+   amg_dist_hier::Pcg &g = D->pcg;
+   hipStream_t s = c->stream;
+   DLevel &v = D->lv[0];
+   g.on = false;
+   g.iter = 0;
+   D->have_state = false; // a running amg_dist_solve_* state ends here
+   D->pre_ready = false;
+   for (int l = 0; l < D->Ld; l++) {
+      DLevel &w = D->lv[l];
+      for (double *p : {w.f, w.u, w.u_alt, w.r_fine}) lzero(D, l, p);
+      w.zero_flag = 0;
+   }
+   for (double *p : {D->r0, g.x, g.p, g.q}) lzero(D, 0, p);
+   AMG_TRY(h2d(s, v.f, f_local, (size_t)v.n * sizeof(double)));
+   if (x0_local) AMG_TRY(h2d(s, g.x, x0_local, (size_t)v.n * sizeof(double)));
+   AMG_TRY(d_spgemv(D, v.A, g.x, v.f, amgk::gemv_mode(-1.0, 1.0), D->r0, nullptr));
+   AMG_TRY(dpcg_precond(D));
+   int np = 0;
+   amgk::sumsq_partials(s, D->r0, v.n, g.part_rr, &np);
+   AMG_TRY(dpcg_finish_dots(D, 1));
+   amgk::vcopy(s, v.u, g.p, 0, v.n);
+   AMG_HIP(hipGetLastError());
+   AMG_TRY(d2h(s, c->h_pinned, D->d_hist, sizeof(double)));
+   g.r0norm = c->h_pinned[0];
+   g.on = true;
+   if (r0norm) *r0norm = g.r0norm;
+   return AMG_OK;
+}
+
+extern "C" int amg_dist_pcg_iterate(amg_dist_hier *D, int k)
+{
+   AMG_ARG(D && D->pcg.on, "amg_dist_pcg_iterate: call amg_dist_pcg_start (or amg_dist_pcg_solve) first");
+   amg_dist_hier::Pcg &g = D->pcg;
+   amg_ctx *c = D->ctx;
+   hipStream_t s = c->stream;
+   DLevel &v = D->lv[0];
+   const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
+   // the cycle's first level-0 sweep rides on the residual update where it is
+   // the zero-guess Jacobi sweep (one pass over r and one clear of u fewer)
+   const bool fz = dpcg_fuse_zero(D);
+   const double *l1 = D->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr;
+   int st = AMG_OK;
+   for (int i = 0; i < k && st == AMG_OK; i++) {
+      int np = 0, np_rr = 0;
+      if ((st = d_spgemv(D, v.A, g.p, nullptr, mv, g.q, nullptr)) != AMG_OK) break;
+      amgk::dot_partials(s, g.p, g.q, v.n, g.part_dot, &np);
+      amgk::pcg_rank_sum(s, g.part_dot, nullptr, np, g.slot);
+      if ((st = xp_allgather(c, s, g.slot, g.gath, sizeof(double))) != AMG_OK) break;
+      amgk::pcg_alpha_ranks(s, g.gath, c->xport->nranks, g.sc, g.ring + g.iter % amgk::PCG_RING);
+      amgk::pcg_update_xr_rows(s, g.x, g.p, D->r0, g.q, v.n, g.sc, g.part_rr, &np_rr, dm_diag(v.A), 0.0, l1,
+                               D->o.smooth_weight, fz ? v.u : nullptr);
+      g.iter++;
+      if ((st = dpcg_precond(D, fz)) != AMG_OK) break;
+      if ((st = dpcg_finish_dots(D, 0)) != AMG_OK) break;
+      amgk::pcg_update_p(s, v.u, g.p, v.n, g.sc);
+   }
+   if (st != AMG_OK) {
+      g.on = false;
+      return st;
+   }
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
+
+extern "C" int amg_dist_pcg_resnorm(amg_dist_hier *D, double *out)
+{
+   AMG_ARG(D && out && D->pcg.on, "amg_dist_pcg_resnorm: no PCG state");
+   amg_ctx *c = D->ctx;
+   AMG_TRY(d2h(c->stream, c->h_pinned, D->d_hist + dpcg_hist_slot(D), sizeof(double)));
+   *out = c->h_pinned[0];
+   return AMG_OK;
+}
+
+extern "C" int amg_dist_pcg_get_x(amg_dist_hier *D, double *x_local)
+{
+   AMG_ARG(D && x_local && D->pcg.on, "amg_dist_pcg_get_x: bad argument or no PCG state");
+   return d2h(D->ctx->stream, x_local, D->pcg.x, (size_t)D->lv[0].n * sizeof(double));
+}
+
+extern "C" int amg_dist_pcg_get_r(amg_dist_hier *D, double *r_local)
+{
+   AMG_ARG(D && r_local && D->pcg.on, "amg_dist_pcg_get_r: bad argument or no PCG state");
+   return d2h(D->ctx->stream, r_local, D->r0, (size_t)D->lv[0].n * sizeof(double));
+}
+
+extern "C" int amg_dist_pcg_scalars(const amg_dist_hier *D, double *alpha, double *beta, double *rho, int cap,
+                                    int *count)
+{
+   AMG_ARG(D && count && cap >= 0 && D->pcg.on, "amg_dist_pcg_scalars: bad argument or no PCG state");
+   const amg_dist_hier::Pcg &g = D->pcg;
+   hipStream_t s = D->ctx->stream;
+   const int m = std::min(std::min(g.iter, cap), amgk::PCG_RING);
+   double *out[3] = {alpha, beta, rho};
+   for (int a = 0; a < 3; a++) {
+      if (!out[a]) continue;
+      // iterations iter - m + 1 .. iter, oldest first (the ring may wrap)
+      for (int j = 0; j < m;) {
+         const int slot = (g.iter - m + j) % amgk::PCG_RING;
+         const int run = std::min(m - j, amgk::PCG_RING - slot);
+         AMG_HIP(hipMemcpyAsync(out[a] + j, g.ring + a * amgk::PCG_RING + slot, run * sizeof(double),
+                                hipMemcpyDeviceToHost, s));
+         j += run;
+      }
+   }
+   AMG_HIP(hipStreamSynchronize(s));
+   *count = m;
+   return AMG_OK;
+}
+
+extern "C" int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, double *x_local, double *reshist,
+                                  int *iters_done)
+{
+   AMG_ARG(D && f_local && x_local, "amg_dist_pcg_solve: null argument");
+   AMG_TRY(amg_dist_pcg_start(D, f_local, x_local, nullptr));
+   const amg_dist_hier::Pcg &g = D->pcg;
+   if (reshist) reshist[0] = g.r0norm;
+   int done = 0;
+   for (int k = 1; k <= D->o.num_cycles; k++) {
+      AMG_TRY(amg_dist_pcg_iterate(D, 1));
+      done = k;
+      if (D->o.check_resnorm == 1) {
+         // every rank reads the same bits (the rank-ordered sum), so all stop together
+         double rn;
+         AMG_TRY(amg_dist_pcg_resnorm(D, &rn));
+         if (reshist) reshist[k] = rn;
+         if (rn / g.r0norm < D->o.tol) break;
+      }
+   }
+   // without the per-iteration read the history comes from the device ring
+   // in one copy (as long as it has not wrapped)
+   if (reshist && D->o.check_resnorm != 1 && done > 0 && done < D->hist_cap - 1)
+      AMG_TRY(d2h(D->ctx->stream, reshist + 1, D->d_hist + 1, done * sizeof(double)));
+   AMG_TRY(amg_dist_pcg_get_x(D, x_local));
+   if (iters_done) *iters_done = done;
    return AMG_OK;
 }
 

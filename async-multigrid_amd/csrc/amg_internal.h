@@ -259,6 +259,9 @@ int amg_mat_finish(amg_mat *A);
 int amg_hier_subcycle(amg_hier *H, hipStream_t s, const double *f_dev, const double **u_dev);
 // InitVectors: zero every level vector of H (start of a new solve)
 int amg_hier_reset(amg_hier *H);
+// every level's iterate u back to zero: the state one preconditioner
+// application starts from (the coarsest iterate otherwise carries over)
+int amg_hier_zero_iterates(amg_hier *H);
 
 // ---------------------------------------------------------------------------
 // kernel launchers (amg_kernels.hip); all asynchronous on stream s
@@ -469,6 +472,7 @@ void reduce_partials(hipStream_t s, const double *partials, int np, double *out,
 // preconditioned CG (amg_pcg.hip): the device scalar block sc and the kernels
 // that read and write it; np <= 1024 partials of the reduction grid
 enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_PQ = 3, PCG_RR = 4, PCG_NSCALARS = 8 };
+constexpr int PCG_RING = 4096; // alpha / beta / rho of the last PCG_RING iterations
 // pq = sum(part); sc[ALPHA] = sc[RHO] / pq (0 where pq = 0), also into *ring_alpha
 void pcg_alpha(hipStream_t s, const double *part, int np, double *sc, double *ring_alpha);
 // *norm = sqrt(sum(part_rr)); rho' = sum(part_rz); sc[BETA] = rho' / sc[RHO] (0 where
@@ -481,6 +485,18 @@ void pcg_beta(hipStream_t s, const double *part_rr, const double *part_rz, int n
 void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
                    const double *sc, double *partials, int *nparts, const amg_mat *A = nullptr,
                    const double *l1 = nullptr, double w = 0.0, double *u0 = nullptr);
+// the same on rows whose diagonal is diag[i] (null: the one value diag_u): a distributed
+// level's owned rows
+void pcg_update_xr_rows(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
+                        const double *sc, double *partials, int *nparts, const double *diag, double diag_u,
+                        const double *l1, double w, double *u0);
+// across ranks (amg_dist_pcg_*): slot[0] = sum(part_a), slot[1] = sum(part_b) (null: one sum)
+// in reduce_partials' order; after the all-gather of the slots, pcg_alpha / pcg_beta on the
+// gathered values v (one per rank; (r.r, r.z) pairs for beta) added in rank order
+void pcg_rank_sum(hipStream_t s, const double *part_a, const double *part_b, int np, double *slot);
+void pcg_alpha_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *ring_alpha);
+void pcg_beta_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *norm, double *ring_beta,
+                    double *ring_rho, int first);
 // p = z + sc[BETA] p
 void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc);
 

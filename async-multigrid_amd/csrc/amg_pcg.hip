@@ -1,5 +1,6 @@
 // amg_pcg.hip -- the preconditioned conjugate-gradient recurrence's own kernels
-// (amg_pcg_* in amg_solver.cpp).  alpha, beta and rho never leave the device:
+// (amg_pcg_* in amg_solver.cpp, amg_dist_pcg_* in amg_dist.cpp).  alpha, beta
+// and rho never leave the device:
 // a single-workgroup kernel finishes each dot product and forms the quotient
 // in the same launch, and the vector kernels read the scalars from device
 // memory.  Every product and sum is rounded on its own (-ffp-contract=off), the
@@ -64,6 +65,63 @@ __global__ __launch_bounds__(256) void pcg_beta_k(const double *__restrict__ par
    const double rr = pcg_sum_partials(part_rr, np, red);
    const double rz = pcg_sum_partials(part_rz, np, red);
    if (threadIdx.x == 0) {
+      *norm = sqrt(rr);
+      sc[PCG_RR] = rr;
+      if (!first) {
+         const double rho = sc[PCG_RHO];
+         const double beta = rho != 0.0 ? rz / rho : 0.0;
+         sc[PCG_BETA] = beta;
+         *ring_beta = beta;
+         *ring_rho = rz;
+      }
+      sc[PCG_RHO] = rz;
+   }
+}
+
+// ---- across ranks (amg_dist_pcg_*) ----------------------------------------------
+// Each rank sums its own rows exactly as above and writes the one double per
+// dot product into its slot; the slots are all-gathered and every rank adds
+// them in rank order, s = 0.0; s += v[r], so all ranks hold the same bits
+// whatever the transport, and one rank holds the bits of the kernels above.
+
+// this rank's sums: slot[0] = sum(part_a), slot[1] = sum(part_b) (part_b may be null)
+__global__ __launch_bounds__(256) void pcg_rank_sum_k(const double *__restrict__ part_a,
+                                                      const double *__restrict__ part_b, int np,
+                                                      double *__restrict__ slot)
+{
+   __shared__ double red[4];
+   const double a = pcg_sum_partials(part_a, np, red);
+   if (threadIdx.x == 0) slot[0] = a;
+   if (part_b) {
+      const double b = pcg_sum_partials(part_b, np, red);
+      if (threadIdx.x == 0) slot[1] = b;
+   }
+}
+
+// pcg_alpha_k on the gathered rank values v[r] of p.q
+__global__ __launch_bounds__(256) void pcg_alpha_ranks_k(const double *__restrict__ v, int nranks,
+                                                         double *__restrict__ sc, double *__restrict__ ring_alpha)
+{
+   if (threadIdx.x == 0) {
+      double pq = 0.0;
+      for (int r = 0; r < nranks; r++) pq += v[r];
+      const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
+      sc[PCG_PQ] = pq;
+      sc[PCG_ALPHA] = alpha;
+      if (ring_alpha) *ring_alpha = alpha;
+   }
+}
+
+// pcg_beta_k on the gathered rank values (v[2 r], v[2 r + 1]) of (r.r, r.z)
+__global__ __launch_bounds__(256) void pcg_beta_ranks_k(const double *__restrict__ v, int nranks,
+                                                        double *__restrict__ sc, double *__restrict__ norm,
+                                                        double *__restrict__ ring_beta,
+                                                        double *__restrict__ ring_rho, int first)
+{
+   if (threadIdx.x == 0) {
+      double rr = 0.0, rz = 0.0;
+      for (int r = 0; r < nranks; r++) rr += v[2 * r];
+      for (int r = 0; r < nranks; r++) rz += v[2 * r + 1];
       *norm = sqrt(rr);
       sc[PCG_RR] = rr;
       if (!first) {
@@ -159,18 +217,43 @@ void pcg_beta(hipStream_t s, const double *part_rr, const double *part_rz, int n
    pcg_beta_k<<<1, 256, 0, s>>>(part_rr, part_rz, np, sc, norm, ring_beta, ring_rho, first);
 }
 
-void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
-                   const double *sc, double *partials, int *nparts, const amg_mat *A, const double *l1, double w,
-                   double *u0)
+void pcg_rank_sum(hipStream_t s, const double *part_a, const double *part_b, int np, double *slot)
+{
+   pcg_rank_sum_k<<<1, 256, 0, s>>>(part_a, part_b, np, slot);
+}
+
+void pcg_alpha_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *ring_alpha)
+{
+   pcg_alpha_ranks_k<<<1, 256, 0, s>>>(v, nranks, sc, ring_alpha);
+}
+
+void pcg_beta_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *norm, double *ring_beta,
+                    double *ring_rho, int first)
+{
+   pcg_beta_ranks_k<<<1, 256, 0, s>>>(v, nranks, sc, norm, ring_beta, ring_rho, first);
+}
+
+void pcg_update_xr_rows(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
+                        const double *sc, double *partials, int *nparts, const double *diag, double diag_u,
+                        const double *l1, double w, double *u0)
 {
    const int nb = pcg_red_blocks(n);
    if (u0) {
-      const PcgZero zg{u0, A->diag_uni ? nullptr : A->diag, l1, A->diag_u, w};
+      const PcgZero zg{u0, diag, l1, diag_u, w};
       pcg_xr_k<true><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, zg);
    } else {
       pcg_xr_k<false><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, PcgZero{});
    }
    *nparts = nb;
+}
+
+void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
+                   const double *sc, double *partials, int *nparts, const amg_mat *A, const double *l1, double w,
+                   double *u0)
+{
+   const bool uni = u0 && A->diag_uni;
+   pcg_update_xr_rows(s, x, p, r, q, n, sc, partials, nparts, u0 && !uni ? A->diag : nullptr,
+                      uni ? A->diag_u : 0.0, l1, w, u0);
 }
 
 void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc)

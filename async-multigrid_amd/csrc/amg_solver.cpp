@@ -1254,6 +1254,16 @@ int amg_hier_reset(amg_hier *H)
    return AMG_OK;
 }
 
+int amg_hier_zero_iterates(amg_hier *H)
+{
+   for (int l = 0; l < H->L; l++) {
+      amgk::vset(H->ctx->stream, H->lv[l].u, 0.0, 0, H->lv[l].n);
+      H->lv[l].zero_flag = 0;
+   }
+   AMG_HIP(hipGetLastError());
+   return AMG_OK;
+}
+
 extern "C" int amg_vcycle(amg_hier *H)
 {
    AMG_ARG(H, "amg_vcycle: null hierarchy");
@@ -1346,7 +1356,7 @@ extern "C" int amg_eigs_power(amg_hier *H, int iters, double *eig_max, double *e
 // r (pcg_fuse_zero), the residual update writes it as well, so the cycle neither
 // clears u nor reads r again.  cheby_flag, delays, graph replay and
 // reuse_outer_residual do not apply.
-constexpr int PCG_RING = 4096; // alpha / beta / rho of the last PCG_RING iterations
+using amgk::PCG_RING;
 
 static int pcg_check(const amg_hier *H, const char *who)
 {

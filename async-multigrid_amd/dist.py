@@ -299,6 +299,60 @@ class DistHier:
         check(lib.amg_dist_solve_resnorm(self.h, C.byref(r)))
         return r.value
 
+    def _local(self, v):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        assert a.size == self.n0
+        return a
+
+    def precond_apply(self, r_local):
+        """z = M^-1 r on this rank's rows: one cycle from a zero state (amg_dist_precond_apply)."""
+        r, z = self._local(r_local), np.empty(self.n0)
+        check(lib.amg_dist_precond_apply(self.h, _dp(r), _dp(z)))
+        return z
+
+    def pcg_solve(self, f_local, x0_local=None):
+        """AMG-preconditioned CG across ranks (amg_dist_pcg_solve): returns (this rank's rows of x,
+        residual-norm history, iterations), the last two the same on every rank."""
+        f = self._local(f_local)
+        x = np.zeros(self.n0) if x0_local is None else self._local(x0_local).copy()
+        hist = np.zeros(self.opts.num_cycles + 1)
+        k = C.c_int()
+        check(lib.amg_dist_pcg_solve(self.h, _dp(f), _dp(x), _dp(hist), C.byref(k)))
+        return x, hist[:k.value + 1], k.value
+
+    def pcg_start(self, f_local, x0_local=None):
+        f = self._local(f_local)
+        x0 = None if x0_local is None else self._local(x0_local)
+        r0 = C.c_double()
+        check(lib.amg_dist_pcg_start(self.h, _dp(f), None if x0 is None else _dp(x0), C.byref(r0)))
+        return r0.value
+
+    def pcg_iterate(self, k):
+        check(lib.amg_dist_pcg_iterate(self.h, int(k)))
+
+    def pcg_resnorm(self):
+        r = C.c_double()
+        check(lib.amg_dist_pcg_resnorm(self.h, C.byref(r)))
+        return r.value
+
+    def pcg_get_x(self):
+        x = np.empty(self.n0)
+        check(lib.amg_dist_pcg_get_x(self.h, _dp(x)))
+        return x
+
+    def pcg_get_r(self):
+        """this rank's rows of the recurrence residual"""
+        r = np.empty(self.n0)
+        check(lib.amg_dist_pcg_get_r(self.h, _dp(r)))
+        return r
+
+    def pcg_scalars(self, cap=4096):
+        """(alpha, beta, rho) of the last min(iterations, cap, 4096) iterations, oldest first."""
+        a, b, r = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        n = C.c_int()
+        check(lib.amg_dist_pcg_scalars(self.h, _dp(a), _dp(b), _dp(r), int(cap), C.byref(n)))
+        return a[:n.value], b[:n.value], r[:n.value]
+
     def async_solve(self, f_local):
         """Asynchronous additive solve (ASYNC_MULTADD / ASYNC_AFACX opts):
         returns (relres, per-level correction counts); u via get_u()."""

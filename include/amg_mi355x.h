@@ -786,6 +786,43 @@ int amg_dist_solve_iterate(amg_dist_hier *D, int k);
 int amg_dist_solve_resnorm(amg_dist_hier *D, double *out);
 int amg_dist_get_u(amg_dist_hier *D, double *u_local);
 int amg_dist_profile_read(amg_dist_hier *D, double *ms, long long *launches, int reset);
+/* ---- AMG-preconditioned conjugate gradients across ranks (-hypre_pcg exists only in
+ * the DMEM driver, DMEM_Main.cpp:363-364, 788-804; DMEM_Setup.cpp:129-165 installs
+ * DMEM_MultCycle from a zero guess as HYPRE PCG's preconditioner on the
+ * rank-partitioned A_fine) ----
+ * amg_pcg_*'s recurrence and semantics on a MULT distributed hierarchy of either
+ * form; vectors are this rank's level-0 rows in host memory.  Every dot product
+ * is each rank's sum over its own rows in amg_vec_dot's order, all-gathered and
+ * added in rank order, s = 0.0; s += v[r]: every rank holds the same bits (so all
+ * ranks stop at the same iteration), the result depends on the row partition
+ * only, not on the transport, and one rank gives the bits of amg_pcg_*.  Two
+ * gathers per iteration (p.q; r.r and r.z together), one at the start.  Collective:
+ * every rank makes the same calls.  ASYNC_* hierarchies and accel_type !=
+ * AMG_NO_ACCEL are refused (AMG_ERR_ARG) before any communication; delays and
+ * reuse_outer_residual do not apply.  A start ends a running amg_dist_solve_*
+ * state, and amg_dist_solve_start (or amg_dist_precond_apply) a running PCG.
+ * z = M^-1 r: one cycle from a zero state on every level (DMEM_Setup.cpp:129-165) */
+int amg_dist_precond_apply(amg_dist_hier *D, const double *r_local, double *z_local);
+/* DMEM_Main.cpp:788-804.  x0_local NULL: x0 = 0.  Returns ||r0|| */
+int amg_dist_pcg_start(amg_dist_hier *D, const double *f_local, const double *x0_local, double *r0norm);
+/* k iterations; no host sync on the RCCL transport (the host transport
+ * synchronises inside its collectives) (DMEM_Main.cpp:788-804) */
+int amg_dist_pcg_iterate(amg_dist_hier *D, int k);
+/* ||r||_2 of the recurrence residual after the last enqueued iteration, the
+ * same bits on every rank (DMEM_Main.cpp:788-804's stopping norm) */
+int amg_dist_pcg_resnorm(amg_dist_hier *D, double *out);
+/* this rank's rows of the iterate, and of the recurrence residual r
+ * (DMEM_Main.cpp:788-804) */
+int amg_dist_pcg_get_x(amg_dist_hier *D, double *x_local);
+int amg_dist_pcg_get_r(amg_dist_hier *D, double *r_local);
+/* as amg_pcg_scalars: the last min(iterations, cap, 4096) alpha / beta / rho, the
+ * same on every rank (DMEM_Main.cpp:788-804) */
+int amg_dist_pcg_scalars(const amg_dist_hier *D, double *alpha, double *beta, double *rho, int cap, int *count);
+/* as amg_pcg_solve: x_local holds x0 on entry and the iterate on return; reshist
+ * holds num_cycles + 1 entries; check_resnorm == 1 stops once
+ * reshist[k] / reshist[0] < tol, on every rank at the same k (DMEM_Main.cpp:788-804) */
+int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, double *x_local, double *reshist,
+                       int *iters_done);
 /* asynchronous additive AMG across GPUs (DMEM_Add DMEM_Add.cpp:20-178, AddCycle
  * :180-329, DMEM_AddCorrect_LocalRes :391-458; SMEM_Async_Add_AMG semantics):
  * hierarchy created with solver ASYNC_MULTADD or ASYNC_AFACX.  Every level runs
