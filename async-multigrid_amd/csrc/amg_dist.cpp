@@ -1325,11 +1325,11 @@ extern "C" int amg_dist_get_u(amg_dist_hier *D, double *u_local)
 // ---- preconditioned CG across ranks (-hypre_pcg: DMEM_Main.cpp:363-364, 788-804; --
 // DMEM_Setup.cpp:129-165 installs DMEM_MultCycle from a zero guess as HYPRE PCG's
 // preconditioner on the rank-partitioned A_fine) --------------------------------------
-// amg_pcg_*'s recurrence (amg_solver.cpp) on this rank's rows: q = A p is the
-// distributed product, M^-1 one dist_vcycle in preconditioner mode, and each dot
-// product is this rank's sum in amg_vec_dot's order, all-gathered and added in
-// rank order by the kernel that forms the quotient (amg_pcg.hip).  Two gathers
-// per iteration: p.q, then (r.r, r.z) together after the preconditioner.
+// amg_pcg.h's recurrence on this rank's rows: q = A p is the distributed product,
+// M^-1 one dist_vcycle in preconditioner mode, and each dot product is this
+// rank's sum in amg_vec_dot's order, all-gathered and added in rank order by the
+// kernel that forms the quotient (amg_pcg.hip).  Two gathers per iteration: p.q,
+// then (r.r, r.z) together after the preconditioner.
 namespace {
 
 int dpcg_check(const amg_dist_hier *D, const char *who)
@@ -1361,39 +1361,35 @@ int dpcg_precond(amg_dist_hier *D, bool zero0_done = false)
    return dist_vcycle(D, true, zero0_done);
 }
 
-int dpcg_alloc(amg_dist_hier *D)
-{
-   amg_dist_hier::Pcg &g = D->pcg;
-   if (!g.x) AMG_TRY(lvec(D, 0, &g.x));
-   if (!g.p) AMG_TRY(lvec(D, 0, &g.p));
-   if (!g.q) AMG_TRY(lvec(D, 0, &g.q));
-   if (!g.sc) AMG_TRY(dvec(D, amgk::PCG_NSCALARS, &g.sc));
-   if (!g.part_rr) AMG_TRY(dvec(D, 1024, &g.part_rr));
-   if (!g.part_dot) AMG_TRY(dvec(D, 1024, &g.part_dot));
-   if (!g.ring) AMG_TRY(dvec(D, 3 * (size_t)amgk::PCG_RING, &g.ring));
-   if (!g.slot) AMG_TRY(dvec(D, 2, &g.slot));
-   if (!g.gath) AMG_TRY(dvec(D, 2 * (size_t)D->ctx->xport->nranks, &g.gath));
-   return AMG_OK;
-}
-
-int dpcg_hist_slot(const amg_dist_hier *D) { return D->pcg.iter % (D->hist_cap - 1); }
-
-// rho (and beta) from r0 . lv[0].u and ||r|| into the history from the r.r
-// partials: one gather of this rank's two sums
-int dpcg_finish_dots(amg_dist_hier *D, int first)
-{
-   amg_dist_hier::Pcg &g = D->pcg;
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   int np = 0;
-   amgk::dot_partials(s, D->r0, D->lv[0].u, D->lv[0].n, g.part_dot, &np); // the r.r partials' grid too
-   amgk::pcg_rank_sum(s, g.part_rr, g.part_dot, np, g.slot);
-   AMG_TRY(xp_allgather(c, s, g.slot, g.gath, 2 * sizeof(double)));
-   const int ring = first ? 0 : (g.iter - 1) % amgk::PCG_RING;
-   amgk::pcg_beta_ranks(s, g.gath, c->xport->nranks, g.sc, D->d_hist + dpcg_hist_slot(D),
-                        g.ring + amgk::PCG_RING + ring, g.ring + 2 * amgk::PCG_RING + ring, first);
-   return AMG_OK;
-}
+// amg_pcg.h's binding: this rank's rows, dot products gathered over the transport
+struct DistPcgBind {
+   amg_dist_hier *D;
+   amg_ctx *c;
+   static constexpr bool gathers = true;
+   int n() const { return D->lv[0].n; }
+   double *r() const { return D->r0; }
+   double *z() const { return D->lv[0].u; }
+   double *hist() const { return D->d_hist; }
+   int hist_cap() const { return D->hist_cap; }
+   int alloc_vec(double **p) { return lvec(D, 0, p); }
+   int alloc(size_t m, double **p) { return dvec(D, m, p); }
+   int apply_A(double *x, const double *b, const amgk::Gemv &mv, double *y)
+   {
+      return d_spgemv(D, D->lv[0].A, x, b, mv, y, nullptr);
+   }
+   int precond(bool zero0_done) { return dpcg_precond(D, zero0_done); }
+   bool fuse_zero() const { return dpcg_fuse_zero(D); }
+   amgk::PcgZero zero_sweep() const
+   {
+      const DLevel &v = D->lv[0];
+      return {nullptr, dm_diag(v.A), D->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr, 0.0, D->o.smooth_weight};
+   }
+   int nranks() const { return c->xport->nranks; }
+   int gather(const double *slot, double *gath, int k)
+   {
+      return xp_allgather(c, c->stream, slot, gath, k * sizeof(double));
+   }
+};
 
 } // namespace
 
@@ -1414,79 +1410,39 @@ extern "C" int amg_dist_pcg_start(amg_dist_hier *D, const double *f_local, const
 {
    AMG_ARG(D && f_local, "amg_dist_pcg_start: null argument");
    AMG_TRY(dpcg_check(D, "amg_dist_pcg_start")); // before any collective: a refused call leaves no peer waiting
-   AMG_TRY(dpcg_alloc(D));
-   amg_ctx *c = D->ctx;
-   amg_dist_hier::Pcg &g = D->pcg;
-   hipStream_t s = c->stream;
-   DLevel &v = D->lv[0];
-   g.on = false;
-   g.iter = 0;
-   D->have_state = false; // a running amg_dist_solve_* state ends here
-   D->pre_ready = false;
-   for (int l = 0; l < D->Ld; l++) {
-      DLevel &w = D->lv[l];
-      for (double *p : {w.f, w.u, w.u_alt, w.r_fine}) lzero(D, l, p);
-      w.zero_flag = 0;
-   }
-   for (double *p : {D->r0, g.x, g.p, g.q}) lzero(D, 0, p);
-   AMG_TRY(h2d(s, v.f, f_local, (size_t)v.n * sizeof(double)));
-   if (x0_local) AMG_TRY(h2d(s, g.x, x0_local, (size_t)v.n * sizeof(double)));
-   AMG_TRY(d_spgemv(D, v.A, g.x, v.f, amgk::gemv_mode(-1.0, 1.0), D->r0, nullptr));
-   AMG_TRY(dpcg_precond(D));
-   int np = 0;
-   amgk::sumsq_partials(s, D->r0, v.n, g.part_rr, &np);
-   AMG_TRY(dpcg_finish_dots(D, 1));
-   amgk::vcopy(s, v.u, g.p, 0, v.n);
-   AMG_HIP(hipGetLastError());
-   AMG_TRY(d2h(s, c->h_pinned, D->d_hist, sizeof(double)));
-   g.r0norm = c->h_pinned[0];
-   g.on = true;
-   if (r0norm) *r0norm = g.r0norm;
-   return AMG_OK;
+   DistPcgBind b{D, D->ctx};
+   // from cleared level vectors and r0, x, p, q (ghost room included); f and x0
+   // (null: zero) come from the host
+   return amg_cg::start(b, D->pcg, [&](const double **fd) {
+      AmgPcg &g = D->pcg;
+      DLevel &v = D->lv[0];
+      D->have_state = false; // a running amg_dist_solve_* state ends here
+      D->pre_ready = false;
+      for (int l = 0; l < D->Ld; l++) {
+         DLevel &w = D->lv[l];
+         for (double *p : {w.f, w.u, w.u_alt, w.r_fine}) lzero(D, l, p);
+         w.zero_flag = 0;
+      }
+      for (double *p : {D->r0, g.x, g.p, g.q}) lzero(D, 0, p);
+      AMG_TRY(h2d(b.c->stream, v.f, f_local, (size_t)v.n * sizeof(double)));
+      if (x0_local) AMG_TRY(h2d(b.c->stream, g.x, x0_local, (size_t)v.n * sizeof(double)));
+      *fd = v.f;
+      return AMG_OK;
+   }, r0norm);
 }
 
 extern "C" int amg_dist_pcg_iterate(amg_dist_hier *D, int k)
 {
    AMG_ARG(D && D->pcg.on, "amg_dist_pcg_iterate: call amg_dist_pcg_start (or amg_dist_pcg_solve) first");
-   amg_dist_hier::Pcg &g = D->pcg;
-   amg_ctx *c = D->ctx;
-   hipStream_t s = c->stream;
-   DLevel &v = D->lv[0];
-   const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   // the cycle's first level-0 sweep rides on the residual update where it is
-   // the zero-guess Jacobi sweep (one pass over r and one clear of u fewer)
-   const bool fz = dpcg_fuse_zero(D);
-   const double *l1 = D->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr;
-   int st = AMG_OK;
-   for (int i = 0; i < k && st == AMG_OK; i++) {
-      int np = 0, np_rr = 0;
-      if ((st = d_spgemv(D, v.A, g.p, nullptr, mv, g.q, nullptr)) != AMG_OK) break;
-      amgk::dot_partials(s, g.p, g.q, v.n, g.part_dot, &np);
-      amgk::pcg_rank_sum(s, g.part_dot, nullptr, np, g.slot);
-      if ((st = xp_allgather(c, s, g.slot, g.gath, sizeof(double))) != AMG_OK) break;
-      amgk::pcg_alpha_ranks(s, g.gath, c->xport->nranks, g.sc, g.ring + g.iter % amgk::PCG_RING);
-      amgk::pcg_update_xr_rows(s, g.x, g.p, D->r0, g.q, v.n, g.sc, g.part_rr, &np_rr, dm_diag(v.A), 0.0, l1,
-                               D->o.smooth_weight, fz ? v.u : nullptr);
-      g.iter++;
-      if ((st = dpcg_precond(D, fz)) != AMG_OK) break;
-      if ((st = dpcg_finish_dots(D, 0)) != AMG_OK) break;
-      amgk::pcg_update_p(s, v.u, g.p, v.n, g.sc);
-   }
-   if (st != AMG_OK) {
-      g.on = false;
-      return st;
-   }
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
+   DistPcgBind b{D, D->ctx};
+   return amg_cg::iterate(b, D->pcg, k);
 }
 
 extern "C" int amg_dist_pcg_resnorm(amg_dist_hier *D, double *out)
 {
    AMG_ARG(D && out && D->pcg.on, "amg_dist_pcg_resnorm: no PCG state");
-   amg_ctx *c = D->ctx;
-   AMG_TRY(d2h(c->stream, c->h_pinned, D->d_hist + dpcg_hist_slot(D), sizeof(double)));
-   *out = c->h_pinned[0];
-   return AMG_OK;
+   DistPcgBind b{D, D->ctx};
+   return amg_cg::resnorm(b, D->pcg, out);
 }
 
 extern "C" int amg_dist_pcg_get_x(amg_dist_hier *D, double *x_local)
@@ -1505,24 +1461,7 @@ extern "C" int amg_dist_pcg_scalars(const amg_dist_hier *D, double *alpha, doubl
                                     int *count)
 {
    AMG_ARG(D && count && cap >= 0 && D->pcg.on, "amg_dist_pcg_scalars: bad argument or no PCG state");
-   const amg_dist_hier::Pcg &g = D->pcg;
-   hipStream_t s = D->ctx->stream;
-   const int m = std::min(std::min(g.iter, cap), amgk::PCG_RING);
-   double *out[3] = {alpha, beta, rho};
-   for (int a = 0; a < 3; a++) {
-      if (!out[a]) continue;
-      // iterations iter - m + 1 .. iter, oldest first (the ring may wrap)
-      for (int j = 0; j < m;) {
-         const int slot = (g.iter - m + j) % amgk::PCG_RING;
-         const int run = std::min(m - j, amgk::PCG_RING - slot);
-         AMG_HIP(hipMemcpyAsync(out[a] + j, g.ring + a * amgk::PCG_RING + slot, run * sizeof(double),
-                                hipMemcpyDeviceToHost, s));
-         j += run;
-      }
-   }
-   AMG_HIP(hipStreamSynchronize(s));
-   *count = m;
-   return AMG_OK;
+   return amg_cg::scalars(D->ctx->stream, D->pcg, alpha, beta, rho, cap, count);
 }
 
 extern "C" int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, double *x_local, double *reshist,
@@ -1530,24 +1469,9 @@ extern "C" int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, doubl
 {
    AMG_ARG(D && f_local && x_local, "amg_dist_pcg_solve: null argument");
    AMG_TRY(amg_dist_pcg_start(D, f_local, x_local, nullptr));
-   const amg_dist_hier::Pcg &g = D->pcg;
-   if (reshist) reshist[0] = g.r0norm;
+   DistPcgBind b{D, D->ctx};
    int done = 0;
-   for (int k = 1; k <= D->o.num_cycles; k++) {
-      AMG_TRY(amg_dist_pcg_iterate(D, 1));
-      done = k;
-      if (D->o.check_resnorm == 1) {
-         // every rank reads the same bits (the rank-ordered sum), so all stop together
-         double rn;
-         AMG_TRY(amg_dist_pcg_resnorm(D, &rn));
-         if (reshist) reshist[k] = rn;
-         if (rn / g.r0norm < D->o.tol) break;
-      }
-   }
-   // without the per-iteration read the history comes from the device ring
-   // in one copy (as long as it has not wrapped)
-   if (reshist && D->o.check_resnorm != 1 && done > 0 && done < D->hist_cap - 1)
-      AMG_TRY(d2h(D->ctx->stream, reshist + 1, D->d_hist + 1, done * sizeof(double)));
+   AMG_TRY(amg_cg::run(b, D->pcg, D->o, reshist, &done));
    AMG_TRY(amg_dist_pcg_get_x(D, x_local));
    if (iters_done) *iters_done = done;
    return AMG_OK;

@@ -1,8 +1,8 @@
 // amg_dist_internal.h -- shared internals of the multi-GPU solve phase.
 //   amg_dist.cpp        transport, the row form's plans and construction, the
 //                       operator launches on a DistMat (dm_*), the one
-//                       synchronous cycle of both forms and the conjugate
-//                       gradients it preconditions (amg_dist_pcg_*)
+//                       synchronous cycle of both forms and amg_pcg.h's
+//                       binding to it (amg_dist_pcg_*)
 //   amg_slab.cpp        the z-slab form: construction, plane exchange, its
 //                       transfers and the fused level-0 residual + restriction
 //   amg_dist_async.cpp  asynchronous additive cycle
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "amg_async.h"
+#include "amg_pcg.h"
 
 struct amg_transport {
    int nranks = 1, rank = 0;
@@ -248,17 +249,8 @@ struct amg_dist_hier {
    amgd::AccelState acc;
    // preconditioned CG (amg_dist_pcg_*): r lives in r0 and z in lv[0].u, as on
    // one GPU; x, p, q are level-0 vectors with ghost room (p is an operand of
-   // the distributed product), allocated by the first start.  slot: this
-   // rank's one or two sums of a dot product; gath: every rank's, in rank order
-   struct Pcg {
-      bool on = false;
-      int iter = 0;
-      double r0norm = 0.0;
-      double *x = nullptr, *p = nullptr, *q = nullptr;
-      double *sc = nullptr, *part_rr = nullptr, *part_dot = nullptr;
-      double *ring = nullptr; // alpha | beta | rho
-      double *slot = nullptr, *gath = nullptr;
-   } pcg;
+   // the distributed product), allocated by the first start
+   AmgPcg pcg;
    GridState grid;
    AmgRaceRecord race; // AMG_SCHED_TIMED level speeds and the last asynchronous solve's records
 };

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -460,7 +461,22 @@ void dc_collect(hipStream_t s, const amg_mat *A, unsigned long long *slots, int 
 void dc_encode(hipStream_t s, const amg_mat *A, const unsigned long long *keys, int T,
                unsigned char *didx, int *anch);
 
-// deterministic reductions
+// deterministic reductions: red_blocks(n) workgroups of 256 lanes, lane t of
+// workgroup b adding i = 256 b + t, += 256 gridDim, then block_sum_256's tree
+inline int red_blocks(int n) { return std::max(1, std::min(1024, (n + 2047) / 2048)); }
+// the workgroup's sum of one double per lane (256 lanes), valid in thread 0
+__device__ __forceinline__ double block_sum_256(double v, double *lds4)
+{
+#pragma unroll
+   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+   __syncthreads();
+   if (lane == 0) lds4[wid] = v;
+   __syncthreads();
+   double s = 0.0;
+   if (threadIdx.x == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+   return s;
+}
 void sumsq_partials(hipStream_t s, const double *x, int n, double *partials, int *nparts);
 void abssum_partials(hipStream_t s, const double *x, int n, double *partials, int *nparts);
 void dot_partials(hipStream_t s, const double *x, const double *y, int n, double *partials,
@@ -479,19 +495,20 @@ void pcg_alpha(hipStream_t s, const double *part, int np, double *sc, double *ri
 // rho = 0), sc[RHO] = rho', both also into the rings; first: sc[RHO] = rho' only
 void pcg_beta(hipStream_t s, const double *part_rr, const double *part_rz, int np, double *sc, double *norm,
               double *ring_beta, double *ring_rho, int first);
-// x += sc[ALPHA] p; r -= sc[ALPHA] q; partials of r.r in dot_partials' order.  u0 != null: also
-// the zero-guess sweep of A (n rows) on the new r into u0 -- jacobi_zero variant 0 on a cleared
-// u0: w r / a_ii where a_ii != 0 and 0 elsewhere, or r / l1
+// the zero-guess Jacobi sweep of a level's rows into a cleared u (jacobi_zero variant 0):
+// u = w r / a for a != 0 and 0 elsewhere, or u = r / l1 under L1 Jacobi
+struct PcgZero {
+   double *u;          // null: no sweep
+   const double *diag; // a_ii (null: the one value a)
+   const double *l1;
+   double a, w;
+};
+// x += sc[ALPHA] p; r -= sc[ALPHA] q; partials of r.r in dot_partials' order; zg.u != null:
+// also that sweep on the new r
 void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
-                   const double *sc, double *partials, int *nparts, const amg_mat *A = nullptr,
-                   const double *l1 = nullptr, double w = 0.0, double *u0 = nullptr);
-// the same on rows whose diagonal is diag[i] (null: the one value diag_u): a distributed
-// level's owned rows
-void pcg_update_xr_rows(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
-                        const double *sc, double *partials, int *nparts, const double *diag, double diag_u,
-                        const double *l1, double w, double *u0);
-// across ranks (amg_dist_pcg_*): slot[0] = sum(part_a), slot[1] = sum(part_b) (null: one sum)
-// in reduce_partials' order; after the all-gather of the slots, pcg_alpha / pcg_beta on the
+                   const double *sc, double *partials, int *nparts, const PcgZero &zg);
+// across ranks: slot[0] = sum(part_a), slot[1] = sum(part_b) (null: one sum) in
+// reduce_partials' order; after the all-gather of the slots, pcg_alpha / pcg_beta on the
 // gathered values v (one per rank; (r.r, r.z) pairs for beta) added in rank order
 void pcg_rank_sum(hipStream_t s, const double *part_a, const double *part_b, int np, double *slot);
 void pcg_alpha_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *ring_alpha);

@@ -59,22 +59,6 @@ static inline int env_int(const char *name, int dflt)
 }
 
 // ---------------------------------------------------------------------------
-// deterministic workgroup reduction of one double per lane (256 lanes)
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum_256(double v, double *lds4)
-{
-#pragma unroll
-   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-   __syncthreads();
-   if (lane == 0) lds4[wid] = v;
-   __syncthreads();
-   double s = 0.0;
-   if (threadIdx.x == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-   return s;
-}
-
-// ---------------------------------------------------------------------------
 // CSR tile kernel
 // ---------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -6504,9 +6488,8 @@ void atomic_add(hipStream_t s, double *u, const double *x, int rb, int re)
 
 // ---------------------------------------------------------------------------
 // deterministic reductions: fixed grid, fixed per-lane order, fixed tree
+// (red_blocks and block_sum_256, amg_internal.h)
 // ---------------------------------------------------------------------------
-static inline int red_blocks(int n) { return std::max(1, std::min(1024, (n + 2047) / 2048)); }
-
 // MODE 0: sum x^2, 1: sum x y, 2: sum |x|
 template <int MODE>
 __global__ __launch_bounds__(256) void partials_k(const double *__restrict__ x,

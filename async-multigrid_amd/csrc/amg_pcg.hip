@@ -1,60 +1,67 @@
-// amg_pcg.hip -- the preconditioned conjugate-gradient recurrence's own kernels
-// (amg_pcg_* in amg_solver.cpp, amg_dist_pcg_* in amg_dist.cpp).  alpha, beta
-// and rho never leave the device:
-// a single-workgroup kernel finishes each dot product and forms the quotient
-// in the same launch, and the vector kernels read the scalars from device
-// memory.  Every product and sum is rounded on its own (-ffp-contract=off), the
-// quotients are IEEE divisions, and the three dot products are summed in
-// amg_vec_dot's order: red_blocks(n) workgroups of 256 lanes, lane t of
-// workgroup b adding i = 256 b + t, += 256 gridDim; block_sum_256's tree; the
-// workgroup partials through the same lane-strided sum in one workgroup.
+// amg_pcg.hip -- the kernels of the preconditioned conjugate-gradient
+// recurrence (amg_pcg.h, which amg_pcg_* in amg_solver.cpp and amg_dist_pcg_*
+// in amg_dist.cpp both run).  alpha, beta and rho never leave the device: a
+// single-workgroup kernel finishes each dot product and forms the quotient in
+// the same launch (pcg_alpha_q / pcg_beta_q, whether the sum came from this
+// GPU's partials or from the ranks' gathered values), and the vector kernels
+// read the scalars from device memory.  Every product and sum is rounded on its
+// own (-ffp-contract=off), the quotients are IEEE divisions, and the three dot
+// products are summed in amg_vec_dot's order: red_blocks(n) workgroups of 256
+// lanes and block_sum_256's tree (amg_internal.h, the same functions
+// partials_k / sum_partials_k call), then the workgroup partials through the
+// same lane-strided sum in one workgroup.
 #include <algorithm>
 
 #include "amg_internal.h"
 
 namespace amgk {
 
-// amg_kernels.hip's reduction grid and workgroup tree (the sums must come out
-// with the bits of partials_k / sum_partials_k)
-static inline int pcg_red_blocks(int n) { return std::max(1, std::min(1024, (n + 2047) / 2048)); }
-
-__device__ __forceinline__ double pcg_block_sum_256(double v, double *lds4)
-{
-#pragma unroll
-   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-   __syncthreads();
-   if (lane == 0) lds4[wid] = v;
-   __syncthreads();
-   double s = 0.0;
-   if (threadIdx.x == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-   return s;
-}
-
 // sum of p[0..np) in sum_partials_k<<<1, 256>>>'s order (valid in thread 0)
 __device__ __forceinline__ double pcg_sum_partials(const double *__restrict__ p, int np, double *lds4)
 {
    double s = 0.0;
    for (int i = threadIdx.x; i < np; i += 256) s += p[i];
-   return pcg_block_sum_256(s, lds4);
+   return block_sum_256(s, lds4);
 }
 
-// pq = sum(part); alpha = rho / pq (0 where pq = 0: a zero right-hand side)
+// the quotient rule (one thread).  alpha = rho / pq (0 where pq = 0: a zero
+// right-hand side)
+__device__ __forceinline__ void pcg_alpha_q(double pq, double *__restrict__ sc, double *__restrict__ ring_alpha)
+{
+   const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
+   sc[PCG_PQ] = pq;
+   sc[PCG_ALPHA] = alpha;
+   if (ring_alpha) *ring_alpha = alpha;
+}
+
+// ||r|| = sqrt(rr) into *norm; rho' = rz; beta = rho' / rho (0 where rho = 0);
+// rho = rho'.  first: the start of a solve (rho only)
+__device__ __forceinline__ void pcg_beta_q(double rr, double rz, double *__restrict__ sc,
+                                           double *__restrict__ norm, double *__restrict__ ring_beta,
+                                           double *__restrict__ ring_rho, int first)
+{
+   *norm = sqrt(rr);
+   sc[PCG_RR] = rr;
+   if (!first) {
+      const double rho = sc[PCG_RHO];
+      const double beta = rho != 0.0 ? rz / rho : 0.0;
+      sc[PCG_BETA] = beta;
+      *ring_beta = beta;
+      *ring_rho = rz;
+   }
+   sc[PCG_RHO] = rz;
+}
+
+// pcg_alpha_q on pq = sum(part)
 __global__ __launch_bounds__(256) void pcg_alpha_k(const double *__restrict__ part, int np,
                                                    double *__restrict__ sc, double *__restrict__ ring_alpha)
 {
    __shared__ double red[4];
    const double pq = pcg_sum_partials(part, np, red);
-   if (threadIdx.x == 0) {
-      const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
-      sc[PCG_PQ] = pq;
-      sc[PCG_ALPHA] = alpha;
-      if (ring_alpha) *ring_alpha = alpha;
-   }
+   if (threadIdx.x == 0) pcg_alpha_q(pq, sc, ring_alpha);
 }
 
-// ||r|| = sqrt(sum(part_rr)) into *norm; rho' = sum(part_rz); beta = rho' / rho
-// (0 where rho = 0); rho = rho'.  first: the start of a solve (rho only)
+// pcg_beta_q on rr = sum(part_rr), rz = sum(part_rz)
 __global__ __launch_bounds__(256) void pcg_beta_k(const double *__restrict__ part_rr,
                                                   const double *__restrict__ part_rz, int np,
                                                   double *__restrict__ sc, double *__restrict__ norm,
@@ -64,21 +71,10 @@ __global__ __launch_bounds__(256) void pcg_beta_k(const double *__restrict__ par
    __shared__ double red[4];
    const double rr = pcg_sum_partials(part_rr, np, red);
    const double rz = pcg_sum_partials(part_rz, np, red);
-   if (threadIdx.x == 0) {
-      *norm = sqrt(rr);
-      sc[PCG_RR] = rr;
-      if (!first) {
-         const double rho = sc[PCG_RHO];
-         const double beta = rho != 0.0 ? rz / rho : 0.0;
-         sc[PCG_BETA] = beta;
-         *ring_beta = beta;
-         *ring_rho = rz;
-      }
-      sc[PCG_RHO] = rz;
-   }
+   if (threadIdx.x == 0) pcg_beta_q(rr, rz, sc, norm, ring_beta, ring_rho, first);
 }
 
-// ---- across ranks (amg_dist_pcg_*) ----------------------------------------------
+// ---- across ranks -----------------------------------------------------------------
 // Each rank sums its own rows exactly as above and writes the one double per
 // dot product into its slot; the slots are all-gathered and every rank adds
 // them in rank order, s = 0.0; s += v[r], so all ranks hold the same bits
@@ -98,21 +94,18 @@ __global__ __launch_bounds__(256) void pcg_rank_sum_k(const double *__restrict__
    }
 }
 
-// pcg_alpha_k on the gathered rank values v[r] of p.q
+// pcg_alpha_q on the gathered rank values v[r] of p.q
 __global__ __launch_bounds__(256) void pcg_alpha_ranks_k(const double *__restrict__ v, int nranks,
                                                          double *__restrict__ sc, double *__restrict__ ring_alpha)
 {
    if (threadIdx.x == 0) {
       double pq = 0.0;
       for (int r = 0; r < nranks; r++) pq += v[r];
-      const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
-      sc[PCG_PQ] = pq;
-      sc[PCG_ALPHA] = alpha;
-      if (ring_alpha) *ring_alpha = alpha;
+      pcg_alpha_q(pq, sc, ring_alpha);
    }
 }
 
-// pcg_beta_k on the gathered rank values (v[2 r], v[2 r + 1]) of (r.r, r.z)
+// pcg_beta_q on the gathered rank values (v[2 r], v[2 r + 1]) of (r.r, r.z)
 __global__ __launch_bounds__(256) void pcg_beta_ranks_k(const double *__restrict__ v, int nranks,
                                                         double *__restrict__ sc, double *__restrict__ norm,
                                                         double *__restrict__ ring_beta,
@@ -122,29 +115,12 @@ __global__ __launch_bounds__(256) void pcg_beta_ranks_k(const double *__restrict
       double rr = 0.0, rz = 0.0;
       for (int r = 0; r < nranks; r++) rr += v[2 * r];
       for (int r = 0; r < nranks; r++) rz += v[2 * r + 1];
-      *norm = sqrt(rr);
-      sc[PCG_RR] = rr;
-      if (!first) {
-         const double rho = sc[PCG_RHO];
-         const double beta = rho != 0.0 ? rz / rho : 0.0;
-         sc[PCG_BETA] = beta;
-         *ring_beta = beta;
-         *ring_rho = rz;
-      }
-      sc[PCG_RHO] = rz;
+      pcg_beta_q(rr, rz, sc, norm, ring_beta, ring_rho, first);
    }
 }
 
 // the cycle's zero-guess Jacobi sweep on the new residual, written where r is
-// still in registers (jacobi_zero variant 0 on a cleared u: u = w r / a for
-// a != 0, 0 otherwise; u = r / l1 for L1 Jacobi)
-struct PcgZero {
-   double *u;          // null: not fused
-   const double *diag; // a_ii (null: the uniform value a)
-   const double *l1;
-   double a, w;
-};
-
+// still in registers (PcgZero, amg_internal.h)
 __device__ __forceinline__ void pcg_zero_sweep(const PcgZero &zg, long long i, double ri)
 {
    if (zg.l1) {
@@ -193,7 +169,7 @@ __global__ __launch_bounds__(256) void pcg_xr_k(double *__restrict__ x, const do
       if (ZG) pcg_zero_sweep(zg, i, ri);
       s += ri * ri;
    }
-   s = pcg_block_sum_256(s, red);
+   s = block_sum_256(s, red);
    if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -233,27 +209,15 @@ void pcg_beta_ranks(hipStream_t s, const double *v, int nranks, double *sc, doub
    pcg_beta_ranks_k<<<1, 256, 0, s>>>(v, nranks, sc, norm, ring_beta, ring_rho, first);
 }
 
-void pcg_update_xr_rows(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
-                        const double *sc, double *partials, int *nparts, const double *diag, double diag_u,
-                        const double *l1, double w, double *u0)
-{
-   const int nb = pcg_red_blocks(n);
-   if (u0) {
-      const PcgZero zg{u0, diag, l1, diag_u, w};
-      pcg_xr_k<true><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, zg);
-   } else {
-      pcg_xr_k<false><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, PcgZero{});
-   }
-   *nparts = nb;
-}
-
 void pcg_update_xr(hipStream_t s, double *x, const double *p, double *r, const double *q, int n,
-                   const double *sc, double *partials, int *nparts, const amg_mat *A, const double *l1, double w,
-                   double *u0)
+                   const double *sc, double *partials, int *nparts, const PcgZero &zg)
 {
-   const bool uni = u0 && A->diag_uni;
-   pcg_update_xr_rows(s, x, p, r, q, n, sc, partials, nparts, u0 && !uni ? A->diag : nullptr,
-                      uni ? A->diag_u : 0.0, l1, w, u0);
+   const int nb = red_blocks(n);
+   if (zg.u)
+      pcg_xr_k<true><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, zg);
+   else
+      pcg_xr_k<false><<<nb, 256, 0, s>>>(x, p, r, q, n, sc, partials, PcgZero{});
+   *nparts = nb;
 }
 
 void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc)

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "amg_async.h"
+#include "amg_pcg.h"
 
 int amg_reduce_to_host(amg_ctx *c, const double *partials, int np, int do_sqrt, double *out);
 int amg_hybrid_jgs_dev(amg_ctx *c, hipStream_t s, const amg_mat *A, const double *f, double *u,
@@ -115,16 +116,8 @@ struct amg_hier {
    // SMEM_Solve.cpp:113), reset by every solve
    std::vector<unsigned long long> delay_rng;
    // preconditioned CG (amg_pcg_*): r lives in r0 and z in lv[0].u, where the
-   // cycle reads and leaves them; x, p, q (n0 each), the device scalar block,
-   // the r.r and p.q / r.z partials and the alpha / beta / rho rings are
-   // allocated by the first amg_pcg_start
-   struct Pcg {
-      double *x = nullptr, *p = nullptr, *q = nullptr, *sc = nullptr, *part_rr = nullptr, *part_dot = nullptr,
-             *ring = nullptr;
-      int iter = 0;
-      bool on = false;
-      double r0norm = 0.0;
-   } pcg;
+   // cycle reads and leaves them; the rest is allocated by the first amg_pcg_start
+   AmgPcg pcg;
    std::vector<void *> allocs;
    AmgProfLog prof;
 };
@@ -1342,21 +1335,14 @@ extern "C" int amg_eigs_power(amg_hier *H, int iters, double *eig_max, double *e
 
 // ---- preconditioned CG (-outer_solver pcg: DMEM_Main.cpp:788-804, --------------
 // DMEM_Setup.cpp:129-165, SMEM_Main.cpp:702-722) ----------------------------------
-// HYPRE's two-norm PCG with one cycle of H's solver from a zero guess as M^-1:
+// amg_pcg.h's recurrence with one cycle of H's solver from a zero guess as M^-1:
 // the multiplicative V-cycle or the BPX cycle in preconditioner mode, or one
-// synchronous additive cycle (u := 0, f_0 := r).  The recurrence, every
-// statement a separately rounded fp64 operation:
-//    r = f - A x0;  z = M^-1 r;  p = z;  rho = r.z;  hist[0] = sqrt(r.r)
-//    q = A p;  alpha = rho / p.q;  x += alpha p;  r -= alpha q;  hist[k] = sqrt(r.r)
-//    z = M^-1 r;  rho' = r.z;  beta = rho' / rho;  rho = rho';  p = z + beta p
-// (alpha, beta = 0 where their divisor is 0: a zero right-hand side stays zero).
-// r lives in r0, where every cycle reads its right-hand side and none writes,
-// and z is lv[0].u, where the cycle leaves it: the preconditioner costs no
-// copy.  Where the cycle's first level-0 sweep is the zero-guess Jacobi sweep on
-// r (pcg_fuse_zero), the residual update writes it as well, so the cycle neither
-// clears u nor reads r again.  cheby_flag, delays, graph replay and
-// reuse_outer_residual do not apply.
-using amgk::PCG_RING;
+// synchronous additive cycle (u := 0, f_0 := r).  r lives in r0, where every
+// cycle reads its right-hand side and none writes, and z is lv[0].u, where the
+// cycle leaves it: the preconditioner costs no copy.  Where the cycle's first
+// level-0 sweep is the zero-guess Jacobi sweep on r (pcg_fuse_zero), the
+// residual update writes it as well, so the cycle neither clears u nor reads r
+// again.  cheby_flag, delays, graph replay and reuse_outer_residual do not apply.
 
 static int pcg_check(const amg_hier *H, const char *who)
 {
@@ -1369,7 +1355,7 @@ static int pcg_check(const amg_hier *H, const char *who)
    return AMG_OK;
 }
 
-// can the residual update write level 0's zero-guess pre-sweep (pcg_update_xr)?
+// can the residual update write level 0's zero-guess pre-sweep?
 // A MULT cycle whose level 0 starts with jacobi_zero on r0
 static bool pcg_fuse_zero(const amg_hier *H)
 {
@@ -1428,34 +1414,35 @@ extern "C" int amg_precond_apply(amg_hier *H, const amg_vec *r, amg_vec *z)
    return AMG_OK;
 }
 
-static int pcg_alloc(amg_hier *H)
-{
-   amg_hier::Pcg &g = H->pcg;
-   const size_t n = (size_t)H->lv[0].n;
-   if (!g.x) AMG_TRY(dalloc(H, n, &g.x));
-   if (!g.p) AMG_TRY(dalloc(H, n, &g.p));
-   if (!g.q) AMG_TRY(dalloc(H, n, &g.q));
-   if (!g.sc) AMG_TRY(dalloc(H, amgk::PCG_NSCALARS, &g.sc));
-   if (!g.part_rr) AMG_TRY(dalloc(H, 1024, &g.part_rr));
-   if (!g.part_dot) AMG_TRY(dalloc(H, 1024, &g.part_dot));
-   if (!g.ring) AMG_TRY(dalloc(H, 3 * (size_t)PCG_RING, &g.ring));
-   return AMG_OK;
-}
-
-static int pcg_hist_slot(const amg_hier *H) { return H->pcg.iter % (H->hist_cap - 1); }
-
-// rho (and beta) from r0 . lv[0].u, ||r|| into the history from the r.r partials
-static void pcg_finish_dots(amg_hier *H, int first)
-{
-   amg_hier::Pcg &g = H->pcg;
-   hipStream_t s = H->ctx->stream;
-   const int n = H->lv[0].n;
-   int np = 0;
-   amgk::dot_partials(s, H->r0, H->lv[0].u, n, g.part_dot, &np); // the r.r partials' grid too
-   const int slot = first ? 0 : (g.iter - 1) % PCG_RING;
-   amgk::pcg_beta(s, g.part_rr, g.part_dot, np, g.sc, H->d_hist + pcg_hist_slot(H), g.ring + PCG_RING + slot,
-                  g.ring + 2 * PCG_RING + slot, first);
-}
+namespace {
+// amg_pcg.h's binding: one GPU, every dot product finished in one launch
+struct PcgBind {
+   amg_hier *H;
+   amg_ctx *c;
+   static constexpr bool gathers = false;
+   int n() const { return H->lv[0].n; }
+   double *r() const { return H->r0; }
+   double *z() const { return H->lv[0].u; }
+   double *hist() const { return H->d_hist; }
+   int hist_cap() const { return H->hist_cap; }
+   int alloc_vec(double **p) { return dalloc(H, (size_t)n(), p); }
+   int alloc(size_t m, double **p) { return dalloc(H, m, p); }
+   int apply_A(const double *x, const double *b, const amgk::Gemv &mv, double *y)
+   {
+      amgk::spgemv(c->stream, H->lv[0].A, x, b, mv, y, 0, n(), nullptr);
+      return AMG_OK;
+   }
+   int precond(bool zero0_done) { return pcg_precond(H, zero0_done); }
+   bool fuse_zero() const { return pcg_fuse_zero(H); }
+   amgk::PcgZero zero_sweep() const
+   {
+      const Level &v = H->lv[0];
+      const bool uni = v.A->diag_uni;
+      return {nullptr, uni ? nullptr : v.A->diag, H->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr,
+              uni ? v.A->diag_u : 0.0, H->o.smooth_weight};
+   }
+};
+} // namespace
 
 extern "C" int amg_pcg_start(amg_hier *H, const amg_vec *f, const amg_vec *x0, double *r0norm)
 {
@@ -1464,68 +1451,26 @@ extern "C" int amg_pcg_start(amg_hier *H, const amg_vec *f, const amg_vec *x0, d
    AMG_ARG(f->n == v.n && x0->n == v.n, "amg_pcg_start: vector size %d/%d vs %d", f->n, x0->n, v.n);
    AMG_TRY(pcg_check(H, "amg_pcg_start"));
    for (auto &a : H->al) AMG_TRY(ensure_xfer_scratch(H, a));
-   AMG_TRY(pcg_alloc(H));
-   amg_ctx *c = H->ctx;
-   amg_hier::Pcg &g = H->pcg;
-   hipStream_t s = c->stream;
-   g.on = false;
-   g.iter = 0;
-   amgk::vcopy(s, x0->d, g.x, 0, v.n);
-   amgk::spgemv(s, v.A, g.x, f->d, amgk::gemv_mode(-1.0, 1.0), H->r0, 0, v.n, nullptr);
-   AMG_TRY(pcg_precond(H));
-   int np = 0;
-   amgk::sumsq_partials(s, H->r0, v.n, g.part_rr, &np);
-   pcg_finish_dots(H, 1);
-   amgk::vcopy(s, H->lv[0].u, g.p, 0, v.n);
-   AMG_HIP(hipGetLastError());
-   AMG_HIP(hipMemcpyAsync(c->h_pinned, H->d_hist, sizeof(double), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   g.r0norm = c->h_pinned[0];
-   g.on = true;
-   if (r0norm) *r0norm = g.r0norm;
-   return AMG_OK;
+   PcgBind b{H, H->ctx};
+   return amg_cg::start(b, H->pcg, [&](const double **fd) {
+      amgk::vcopy(b.c->stream, x0->d, H->pcg.x, 0, v.n);
+      *fd = f->d;
+      return AMG_OK;
+   }, r0norm);
 }
 
 extern "C" int amg_pcg_iterate(amg_hier *H, int k)
 {
    AMG_ARG(H && H->pcg.on, "amg_pcg_iterate: call amg_pcg_start (or amg_pcg_solve) first");
-   amg_hier::Pcg &g = H->pcg;
-   hipStream_t s = H->ctx->stream;
-   Level &v = H->lv[0];
-   const amgk::Gemv mv = amgk::gemv_mode(1.0, 0.0);
-   // the cycle's first level-0 sweep rides on the residual update where it is
-   // the zero-guess Jacobi sweep (one pass over r and one clear of u fewer)
-   const bool fz = pcg_fuse_zero(H);
-   const double *l1 = H->o.smoother == AMG_L1_JACOBI ? v.l1 : nullptr;
-   for (int i = 0; i < k; i++) {
-      int np = 0, np_rr = 0;
-      amgk::spgemv(s, v.A, g.p, nullptr, mv, g.q, 0, v.n, nullptr);
-      amgk::dot_partials(s, g.p, g.q, v.n, g.part_dot, &np);
-      amgk::pcg_alpha(s, g.part_dot, np, g.sc, g.ring + g.iter % PCG_RING);
-      amgk::pcg_update_xr(s, g.x, g.p, H->r0, g.q, v.n, g.sc, g.part_rr, &np_rr, v.A, l1, H->o.smooth_weight,
-                          fz ? v.u : nullptr);
-      g.iter++;
-      const int st = pcg_precond(H, fz);
-      if (st != AMG_OK) {
-         g.on = false;
-         return st;
-      }
-      pcg_finish_dots(H, 0);
-      amgk::pcg_update_p(s, H->lv[0].u, g.p, v.n, g.sc);
-   }
-   AMG_HIP(hipGetLastError());
-   return AMG_OK;
+   PcgBind b{H, H->ctx};
+   return amg_cg::iterate(b, H->pcg, k);
 }
 
 extern "C" int amg_pcg_resnorm(amg_hier *H, double *out)
 {
    AMG_ARG(H && out && H->pcg.on, "amg_pcg_resnorm: no PCG state");
-   amg_ctx *c = H->ctx;
-   AMG_HIP(hipMemcpyAsync(c->h_pinned, H->d_hist + pcg_hist_slot(H), sizeof(double), hipMemcpyDeviceToHost,
-                          c->stream));
-   AMG_HIP(hipStreamSynchronize(c->stream));
-   *out = c->h_pinned[0];
-   return AMG_OK;
+   PcgBind b{H, H->ctx};
+   return amg_cg::resnorm(b, H->pcg, out);
 }
 
 extern "C" int amg_pcg_get_x(amg_hier *H, amg_vec *x)
@@ -1539,48 +1484,16 @@ extern "C" int amg_pcg_get_x(amg_hier *H, amg_vec *x)
 extern "C" int amg_pcg_scalars(const amg_hier *H, double *alpha, double *beta, double *rho, int cap, int *count)
 {
    AMG_ARG(H && count && cap >= 0 && H->pcg.on, "amg_pcg_scalars: bad argument or no PCG state");
-   const amg_hier::Pcg &g = H->pcg;
-   hipStream_t s = H->ctx->stream;
-   const int m = std::min(std::min(g.iter, cap), PCG_RING);
-   double *out[3] = {alpha, beta, rho};
-   for (int a = 0; a < 3; a++) {
-      if (!out[a]) continue;
-      // iterations iter - m + 1 .. iter, oldest first (the ring may wrap)
-      for (int j = 0; j < m;) {
-         const int slot = (g.iter - m + j) % PCG_RING;
-         const int run = std::min(m - j, PCG_RING - slot);
-         AMG_HIP(hipMemcpyAsync(out[a] + j, g.ring + a * PCG_RING + slot, run * sizeof(double),
-                                hipMemcpyDeviceToHost, s));
-         j += run;
-      }
-   }
-   AMG_HIP(hipStreamSynchronize(s));
-   *count = m;
-   return AMG_OK;
+   return amg_cg::scalars(H->ctx->stream, H->pcg, alpha, beta, rho, cap, count);
 }
 
 extern "C" int amg_pcg_solve(amg_hier *H, const amg_vec *f, amg_vec *x, double *reshist, int *iters_done)
 {
    AMG_ARG(H && f && x, "amg_pcg_solve: null argument");
-   amg_ctx *c = H->ctx;
    AMG_TRY(amg_pcg_start(H, f, x, nullptr));
-   const amg_hier::Pcg &g = H->pcg;
-   if (reshist) reshist[0] = g.r0norm;
+   PcgBind b{H, H->ctx};
    int done = 0;
-   for (int k = 1; k <= H->o.num_cycles; k++) {
-      AMG_TRY(amg_pcg_iterate(H, 1));
-      done = k;
-      if (H->o.check_resnorm == 1) {
-         double rn;
-         AMG_TRY(amg_pcg_resnorm(H, &rn));
-         if (reshist) reshist[k] = rn;
-         if (rn / g.r0norm < H->o.tol) break;
-      }
-   }
-   // without the per-iteration read the history comes from the device ring
-   // in one copy (as long as it has not wrapped)
-   if (reshist && H->o.check_resnorm != 1 && done > 0 && done < H->hist_cap - 1)
-      AMG_HIP(hipMemcpyAsync(reshist + 1, H->d_hist + 1, done * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   AMG_TRY(amg_cg::run(b, H->pcg, H->o, reshist, &done));
    AMG_TRY(amg_pcg_get_x(H, x));
    if (iters_done) *iters_done = done;
    return AMG_OK;

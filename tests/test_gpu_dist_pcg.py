@@ -190,7 +190,7 @@ def test_slab_form(amg, oracle):
 
 
 # ---- 5. one rank is one GPU ----------------------------------------------------------
-def single_gpu_pcg(amg, ctx, gen, opts, f, iters):
+def single_gpu_pcg(amg, ctx, gen, opts, f, iters, name):
     def make():
         H = amg.build_hierarchy(ctx, gen, opts)
         fv, xv, out = ctx.vec(f), ctx.vec(np.zeros(f.size)), ctx.vec(f.size)
@@ -204,16 +204,19 @@ def single_gpu_pcg(amg, ctx, gen, opts, f, iters):
         for v in (fv, xv, out):
             v.free()
         return x, sc, np.array(hist)
-    return cached(("single_gpu_pcg", f.size, iters), make)
+    return cached(("single_gpu_pcg", name, f.size, iters), make)
 
 
+@pytest.mark.parametrize("name,n", [("mult_jacobi", 24), ("mult_l1", 16)])
 @pytest.mark.parametrize("rccl", [False, True])
-def test_one_rank_is_one_gpu(amg, oracle, ctx, rccl):
-    """x, alpha / beta / rho and the norms (the same kernel path: 0.0 + v is v) of Hier.pcg_*"""
-    gen, L, host = gen_host(amg, oracle, (24, 24, 24))
-    opts = case_opts(amg, "mult_jacobi", num_cycles=ITERS)
-    f = amg.rhs_rand(0, 24 ** 3)
-    x1, sc1, h1 = single_gpu_pcg(amg, ctx, gen, opts, f, ITERS)
+def test_one_rank_is_one_gpu(amg, oracle, ctx, rccl, name, n):
+    """x, alpha / beta / rho and the norms (the same kernel path: 0.0 + v is v) of Hier.pcg_*.  The two
+    sides hand the fused zero-guess sweep different operands: the diagonal's one value (or a_ii) on one
+    GPU, the owned rows' a_ii across ranks, the l1 norms under L1 Jacobi on both"""
+    gen, L, host = gen_host(amg, oracle, (n, n, n))
+    opts = case_opts(amg, name, num_cycles=ITERS)
+    f = amg.rhs_rand(0, n ** 3)
+    x1, sc1, h1 = single_gpu_pcg(amg, ctx, gen, opts, f, ITERS, name)
     (t,) = ranks(amg, 1, structured(amg, gen, opts), drive(f, ITERS), rccl=rccl)
     assert_bitwise(t["xs"][ITERS], x1, "x")
     for a, b, what in zip(t["sc"], sc1, ("alpha", "beta", "rho")):
