@@ -58,6 +58,39 @@ def default_opts(**kw):
 
 
 
+def lehmer_stream(n, seed=1, skip=0):
+    """u[j] = w_{skip + j + 1} / (2^31 - 1) of w <- 16807 w mod (2^31 - 1) from w_0 = seed (amg_lehmer_stream)."""
+    out = np.zeros(max(int(n), 1))
+    check(lib.amg_lehmer_stream(int(seed), int(skip), int(n), _dp(out)))
+    return out[:int(n)]
+
+
+def lanczos_extremes(alpha, beta, full=False):
+    """(emax, emin) of the Lanczos tridiagonal of the CG scalars alpha, beta (amg_lanczos_extremes:
+    Sturm bisection); full: (emax, emin, tridiag, trioffd)."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    k = a.size
+    assert b.size >= k
+    td, to = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+    emax, emin = C.c_double(), C.c_double()
+    check(lib.amg_lanczos_extremes(k, _dp(a), _dp(b), _dp(td), _dp(to), C.byref(emax), C.byref(emin)))
+    return (emax.value, emin.value, td[:k], to[:k]) if full else (emax.value, emin.value)
+
+
+def _eigs_cg(call, n, iters, scale, r0):
+    """(emax, emin, alpha, beta, gamma, k) of one amg_eigs_cg / amg_dist_eigs_cg call on n rows"""
+    iters = int(iters)
+    if r0 is not None:
+        r0 = np.ascontiguousarray(r0, dtype=np.float64)
+        assert r0.size == n
+    a, b, g = np.zeros(max(iters, 1)), np.zeros(max(iters, 1)), np.zeros(max(iters, 0) + 1)
+    emax, emin, k = C.c_double(), C.c_double(), C.c_int()
+    check(call(int(scale), iters, None if r0 is None else _dp(r0), C.byref(emax), C.byref(emin), _dp(a), _dp(b),
+               _dp(g), C.byref(k)))
+    return emax.value, emin.value, a[:iters], b[:iters], g, k.value
+
+
 def _times_flat(times):
     n = np.array([len(t) for t in times], dtype=np.int32)
     flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64) for t in times] + [np.zeros(1)]))
@@ -206,6 +239,17 @@ class Context:
 
     def csr(self, nrows, ncols, rowptr, col, val, diag_first=1):
         return Mat.register(self, nrows, ncols, rowptr, col, val, diag_first)
+
+    def eigs_cg(self, A, iters=20, scale=1, r0=None):
+        """CG-Lanczos estimate of the extreme eigenvalues of D^-1 A (scale=1) or A (scale=0)
+        (amg_eigs_cg): (emax, emin, alpha, beta, gamma, k) -- the whole alpha / beta / gamma
+        history and the number k of leading iterations the extremes come from."""
+        return _eigs_cg(lambda *a: lib.amg_eigs_cg(self.h, A.h, *a), A.nrows, iters, scale, r0)
+
+    def optimal_jacobi_weight(self, A, iters=20):
+        """1 / emax of eigs_cg(A, iters): the weight the reference's distributed driver gives
+        weighted Jacobi by default (DMEM_Setup.cpp:77-87); put it into opts.smooth_weight."""
+        return 1.0 / self.eigs_cg(A, iters)[0]
 
     def vec(self, n_or_array):
         if isinstance(n_or_array, (int, np.integer)):
@@ -464,6 +508,12 @@ class Hier:
         n = C.c_int()
         check(lib.amg_pcg_scalars(self.h, _dp(a), _dp(b), _dp(r), int(cap), C.byref(n)))
         return a[:n.value], b[:n.value], r[:n.value]
+
+    def pcg_eigs(self):
+        """(emax, emin, k) of M^-1 A from the running PCG's scalars (amg_pcg_eigs)."""
+        emax, emin, k = C.c_double(), C.c_double(), C.c_int()
+        check(lib.amg_pcg_eigs(self.h, C.byref(emax), C.byref(emin), C.byref(k)))
+        return emax.value, emin.value, k.value
 
     def profile(self, reset=True):
         ms = np.zeros(5)

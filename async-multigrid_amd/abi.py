@@ -178,6 +178,10 @@ PROTOTYPES = {
     "amg_pcg_resnorm": (_i, [_p, _dp]),
     "amg_pcg_get_x": (_i, [_p, _p]),
     "amg_pcg_scalars": (_i, [_p, _dp, _dp, _dp, _i, _ip]),
+    "amg_pcg_eigs": (_i, [_p, _dp, _dp, _ip]),
+    "amg_eigs_cg": (_i, [_p, _p, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "amg_lanczos_extremes": (_i, [_i, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "amg_lehmer_stream": (_i, [_ll, _ll, _ll, _dp]),
     "amg_hier_profile_read": (_i, [_p, _dp, _llp, _i]),
     "amg_gen_create": (_i, [_i, _i, _i, _i, _i, _i, _pp]),
     "amg_gen_free": (_i, [_p]),
@@ -225,6 +229,8 @@ PROTOTYPES = {
     "amg_dist_pcg_get_r": (_i, [_p, _dp]),
     "amg_dist_pcg_scalars": (_i, [_p, _dp, _dp, _dp, _i, _ip]),
     "amg_dist_pcg_solve": (_i, [_p, _dp, _dp, _dp, _ip]),
+    "amg_dist_pcg_eigs": (_i, [_p, _dp, _dp, _ip]),
+    "amg_dist_eigs_cg": (_i, [_p, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "amg_dist_hier_free": (_i, [_p]),
     "amg_dist_profile_read": (_i, [_p, _dp, _llp, _i]),
     "amg_dist_fine_spmv": (_i, [_p, _i, _dp]),

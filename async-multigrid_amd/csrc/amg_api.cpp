@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "amg_async.h"
+#include "amg_eig.h"
 
 #include <csignal>
 #include <execinfo.h>
@@ -1471,6 +1472,145 @@ extern "C" int amg_matvec_timed(amg_ctx *c, const amg_mat *A, const amg_vec *x, 
       return AMG_OK;
    };
    return amg_timed_reps(c->stream, reps, spmv, ms);
+}
+
+// ---------------------------------------------------------------------------
+// CG-Lanczos eigenvalue estimate (amg_eig.h; DMEM_Setup.cpp:77-87)
+// ---------------------------------------------------------------------------
+extern "C" int amg_lehmer_stream(long long seed, long long skip, long long n, double *out)
+{
+   constexpr unsigned long long m = 2147483647ULL, a = 16807ULL;
+   AMG_ARG(seed >= 1 && seed < (long long)m && skip >= 0 && n >= 0 && (out || n == 0),
+           "amg_lehmer_stream: seed %lld outside [1, 2^31 - 2], or skip %lld / n %lld negative, or null out", seed,
+           skip, n);
+   // w <- a^skip w mod m by squaring (every product below 2^62)
+   unsigned long long w = (unsigned long long)seed, f = a;
+   for (unsigned long long e = (unsigned long long)skip; e; e >>= 1) {
+      if (e & 1) w = w * f % m;
+      f = f * f % m;
+   }
+   for (long long i = 0; i < n; i++) {
+      w = a * w % m;
+      out[i] = (double)w / 2147483647.0;
+   }
+   return AMG_OK;
+}
+
+// eigenvalues of the k x k tridiagonal (td, to) below x, a zero pivot taken as -DBL_MIN
+static int sturm_count(int k, const double *td, const double *to, double x)
+{
+   int cnt = 0;
+   double q = td[0] - x;
+   if (q == 0.0) q = -DBL_MIN;
+   if (q < 0.0) cnt++;
+   for (int i = 1; i < k; i++) {
+      q = (td[i] - x) - (to[i] * to[i]) / q;
+      if (q == 0.0) q = -DBL_MIN;
+      if (q < 0.0) cnt++;
+   }
+   return cnt;
+}
+
+extern "C" int amg_lanczos_extremes(int k, const double *alpha, const double *beta, double *tridiag,
+                                    double *trioffd, double *eig_max, double *eig_min)
+{
+   AMG_ARG(alpha && beta && tridiag && trioffd && eig_max && eig_min, "amg_lanczos_extremes: null argument");
+   if (k < 1)
+      return amg_set_error(AMG_ERR_UNSUPPORTED, "amg_lanczos_extremes: k = %d: no iteration to estimate from", k);
+   for (int i = 0; i < k; i++)
+      AMG_ARG(std::isfinite(alpha[i]) && alpha[i] != 0.0 && (i == k - 1 || (std::isfinite(beta[i]) && beta[i] >= 0.0)),
+              "amg_lanczos_extremes: alpha[%d] = %g, beta[%d] = %g: alpha must be finite and non-zero, beta finite "
+              "and not negative", i, alpha[i], i, beta[i]);
+   tridiag[0] = 1.0 / alpha[0];
+   trioffd[0] = 0.0;
+   for (int i = 1; i < k; i++) {
+      const double ia = 1.0 / alpha[i - 1];
+      tridiag[i] = ia * beta[i - 1] + 1.0 / alpha[i];
+      trioffd[i] = ia * std::sqrt(beta[i - 1]);
+   }
+   double lo = 0.0, hi = 0.0;
+   for (int i = 0; i < k; i++) {
+      const double rad = std::fabs(trioffd[i]) + (i + 1 < k ? std::fabs(trioffd[i + 1]) : 0.0);
+      const double a = tridiag[i] - rad, b = tridiag[i] + rad;
+      if (i == 0 || a < lo) lo = a;
+      if (i == 0 || b > hi) hi = b;
+   }
+   AMG_ARG(std::isfinite(lo) && std::isfinite(hi), "amg_lanczos_extremes: the tridiagonal is not finite");
+   // bisect [l, h] until the midpoint is one of its ends; below(m): m replaces h, else l
+   auto bisect = [&](auto below, double *l, double *h) {
+      *l = lo, *h = hi;
+      for (double m = 0.5 * (*l + *h); *l < m && m < *h; m = 0.5 * (*l + *h)) *(below(m) ? h : l) = m;
+   };
+   double l, h;
+   bisect([&](double m) { return sturm_count(k, tridiag, trioffd, m) == k; }, &l, &h);
+   *eig_max = h; // the upper end: every eigenvalue lies below it
+   bisect([&](double m) { return sturm_count(k, tridiag, trioffd, m) >= 1; }, &l, &h);
+   *eig_min = l; // the lower end: no eigenvalue lies below it
+   return AMG_OK;
+}
+
+namespace {
+// amg_eig.h's binding: one registered matrix on one GPU; everything it allocates
+// lives for one call
+struct EigBind {
+   amg_ctx *c;
+   const amg_mat *A;
+   std::vector<void *> owned;
+   static constexpr bool gathers = false;
+   ~EigBind()
+   {
+      for (void *p : owned) (void)hipFree(p);
+   }
+   int n() const { return A->nrows; }
+   const double *diag() const { return A->diag; }
+   int alloc(size_t m, double **p)
+   {
+      const size_t bytes = std::max<size_t>(m, 1) * sizeof(double);
+      hipError_t e = hipMalloc(p, bytes);
+      if (e != hipSuccess)
+         return amg_set_error(AMG_ERR_OOM, "amg_eigs_cg: allocation of %zu doubles: %s", m, hipGetErrorString(e));
+      owned.push_back(*p);
+      AMG_HIP(hipMemsetAsync(*p, 0, bytes, c->stream));
+      return AMG_OK;
+   }
+   int alloc_vec(double **p) { return alloc((size_t)A->ncols, p); }
+   int apply_A(const double *x, double *y)
+   {
+      amgk::spgemv(c->stream, A, x, nullptr, amgk::gemv_mode(1.0, 0.0), y, 0, A->nrows, nullptr);
+      return AMG_OK;
+   }
+};
+} // namespace
+
+int amg_eig_start_vector(hipStream_t s, double *r, const double *r0, long long row0, int n)
+{
+   std::vector<double> u;
+   if (!r0) {
+      u.resize(std::max(n, 1));
+      AMG_TRY(amg_lehmer_stream(1, row0, n, u.data()));
+      for (int i = 0; i < n; i++) u[i] = 2.0 * u[i] - 1.0;
+      r0 = u.data();
+   }
+   if (n > 0) AMG_HIP(hipMemcpyAsync(r, r0, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+   AMG_HIP(hipStreamSynchronize(s)); // u is released on return
+   return AMG_OK;
+}
+
+extern "C" int amg_eigs_cg(amg_ctx *c, const amg_mat *A, int scale, int max_iter, const double *r0, double *eig_max,
+                           double *eig_min, double *alpha, double *beta, double *gamma, int *iters)
+{
+   AMG_ARG(c && A && eig_max && eig_min, "amg_eigs_cg: null argument");
+   AMG_ARG(A->nrows == A->ncols && A->nrows >= 1, "amg_eigs_cg: the matrix is %d x %d (square, not empty)", A->nrows,
+           A->ncols);
+   AMG_ARG((scale == 0 || scale == 1) && max_iter >= 1 && max_iter <= amgk::PCG_RING,
+           "amg_eigs_cg: scale %d (0 or 1), max_iter %d (1 .. %d)", scale, max_iter, amgk::PCG_RING);
+   EigBind b{c, A, {}};
+   AmgEig g;
+   const int st = amg_eig::run(b, g, "amg_eigs_cg", scale, max_iter, [&](double *r) {
+      return amg_eig_start_vector(c->stream, r, r0, 0, A->nrows);
+   }, eig_max, eig_min, alpha, beta, gamma, iters);
+   (void)hipStreamSynchronize(c->stream); // nothing of g is in flight when b frees it
+   return st;
 }
 
 // measurement helpers (declared in the header): PMC calibration streams

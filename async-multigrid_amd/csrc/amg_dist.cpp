@@ -1477,6 +1477,56 @@ extern "C" int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, doubl
    return AMG_OK;
 }
 
+extern "C" int amg_dist_pcg_eigs(const amg_dist_hier *D, double *eig_max, double *eig_min, int *iters)
+{
+   AMG_ARG(D && eig_max && eig_min && D->pcg.on, "amg_dist_pcg_eigs: bad argument or no PCG state");
+   return amg_eig::pcg_extremes("amg_dist_pcg_eigs", D->ctx->stream, D->pcg, eig_max, eig_min, iters);
+}
+
+// ---- the CG-Lanczos eigenvalue estimate across ranks (DMEM_Setup.cpp:77-87: -----------
+// hypre_ParCSRMaxEigEstimateCG on the rank-partitioned A_fine) ---------------------------
+// amg_eig.h's recurrence on this rank's rows of level 0, either form: q = A p is the
+// distributed product, the two dot products per iteration are gathered as PCG's are
+namespace {
+struct DistEigBind {
+   amg_dist_hier *D;
+   amg_ctx *c;
+   static constexpr bool gathers = true;
+   int n() const { return D->lv[0].n; }
+   const double *diag() const { return dm_diag(D->lv[0].A); }
+   int alloc_vec(double **p)
+   {
+      AMG_TRY(lvec(D, 0, p));
+      lzero(D, 0, *p);
+      return AMG_OK;
+   }
+   int alloc(size_t m, double **p) { return dvec(D, m, p); }
+   int apply_A(double *x, double *y)
+   {
+      return d_spgemv(D, D->lv[0].A, x, nullptr, amgk::gemv_mode(1.0, 0.0), y, nullptr);
+   }
+   int nranks() const { return c->xport->nranks; }
+   int gather(const double *slot, double *gath, int k) { return gather_bytes(slot, gath, k * sizeof(double)); }
+   int gather_bytes(const void *send, void *recv, long long bytes)
+   {
+      return xp_allgather(c, c->stream, send, recv, bytes);
+   }
+};
+} // namespace
+
+extern "C" int amg_dist_eigs_cg(amg_dist_hier *D, int scale, int max_iter, const double *r0_local, double *eig_max,
+                                double *eig_min, double *alpha, double *beta, double *gamma, int *iters)
+{
+   AMG_ARG(D && eig_max && eig_min, "amg_dist_eigs_cg: null argument");
+   AMG_ARG((scale == 0 || scale == 1) && max_iter >= 1 && max_iter <= amgk::PCG_RING,
+           "amg_dist_eigs_cg: scale %d (0 or 1), max_iter %d (1 .. %d)", scale, max_iter, amgk::PCG_RING);
+   AMG_ARG(D->Ld >= 1, "amg_dist_eigs_cg: level 0 is not distributed");
+   DistEigBind b{D, D->ctx};
+   return amg_eig::run(b, D->eig, "amg_dist_eigs_cg", scale, max_iter, [&](double *r) {
+      return amg_eig_start_vector(D->ctx->stream, r, r0_local, D->lv[0].row0, D->lv[0].n);
+   }, eig_max, eig_min, alpha, beta, gamma, iters);
+}
+
 extern "C" int amg_dist_profile_read(amg_dist_hier *D, double *ms, long long *launches, int reset)
 {
    AMG_ARG(D, "amg_dist_profile_read: null hierarchy");

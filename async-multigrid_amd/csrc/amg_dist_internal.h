@@ -17,6 +17,7 @@
 
 #include "amg_async.h"
 #include "amg_pcg.h"
+#include "amg_eig.h"
 
 struct amg_transport {
    int nranks = 1, rank = 0;
@@ -251,6 +252,9 @@ struct amg_dist_hier {
    // one GPU; x, p, q are level-0 vectors with ghost room (p is an operand of
    // the distributed product), allocated by the first start
    AmgPcg pcg;
+   // the CG-Lanczos estimate on level 0 (amg_dist_eigs_cg): its own r, p, q and
+   // scalars, allocated by the first call; no solve's state is touched
+   AmgEig eig;
    GridState grid;
    AmgRaceRecord race; // AMG_SCHED_TIMED level speeds and the last asynchronous solve's records
 };

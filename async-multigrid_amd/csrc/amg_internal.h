@@ -487,8 +487,49 @@ void reduce_partials(hipStream_t s, const double *partials, int np, double *out,
 
 // preconditioned CG (amg_pcg.hip): the device scalar block sc and the kernels
 // that read and write it; np <= 1024 partials of the reduction grid
-enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_PQ = 3, PCG_RR = 4, PCG_NSCALARS = 8 };
+enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_PQ = 3, PCG_RR = 4, PCG_RHO0 = 5, PCG_NSCALARS = 8 };
 constexpr int PCG_RING = 4096; // alpha / beta / rho of the last PCG_RING iterations
+// The finish of a dot product and the one definition of each quotient rule, shared by
+// amg_pcg.hip and amg_eig.hip.
+// sum of p[0..np) in sum_partials_k<<<1, 256>>>'s order (valid in thread 0)
+__device__ __forceinline__ double pcg_sum_partials(const double *__restrict__ p, int np, double *lds4)
+{
+   double s = 0.0;
+   for (int i = threadIdx.x; i < np; i += 256) s += p[i];
+   return block_sum_256(s, lds4);
+}
+
+// the quotient rule (one thread).  alpha = rho / pq (0 where pq = 0: a zero
+// right-hand side)
+__device__ __forceinline__ void pcg_alpha_q(double pq, double *__restrict__ sc, double *__restrict__ ring_alpha)
+{
+   const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
+   sc[PCG_PQ] = pq;
+   sc[PCG_ALPHA] = alpha;
+   if (ring_alpha) *ring_alpha = alpha;
+}
+
+// ||r|| = sqrt(rr) into *norm (null: not wanted); rho' = rz; beta = rho' / rho
+// (0 where rho = 0); rho = rho'.  first: the start of a solve (rho only, kept in
+// sc[PCG_RHO0] as well: the ring holds the later ones)
+__device__ __forceinline__ void pcg_beta_q(double rr, double rz, double *__restrict__ sc,
+                                           double *__restrict__ norm, double *__restrict__ ring_beta,
+                                           double *__restrict__ ring_rho, int first)
+{
+   if (norm) *norm = sqrt(rr);
+   sc[PCG_RR] = rr;
+   if (!first) {
+      const double rho = sc[PCG_RHO];
+      const double beta = rho != 0.0 ? rz / rho : 0.0;
+      sc[PCG_BETA] = beta;
+      *ring_beta = beta;
+      *ring_rho = rz;
+   } else {
+      sc[PCG_RHO0] = rz;
+   }
+   sc[PCG_RHO] = rz;
+}
+
 // pq = sum(part); sc[ALPHA] = sc[RHO] / pq (0 where pq = 0), also into *ring_alpha
 void pcg_alpha(hipStream_t s, const double *part, int np, double *sc, double *ring_alpha);
 // *norm = sqrt(sum(part_rr)); rho' = sum(part_rz); sc[BETA] = rho' / sc[RHO] (0 where
@@ -516,6 +557,25 @@ void pcg_beta_ranks(hipStream_t s, const double *v, int nranks, double *sc, doub
                     double *ring_rho, int first);
 // p = z + sc[BETA] p
 void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc);
+
+// CG-Lanczos eigenvalue estimate (amg_eig.hip; the recurrence is amg_eig.h): CG on A
+// preconditioned by its diagonal d (null: d = 1, no division), no right-hand side and no
+// iterate.  sc is a PCG scalar block with gamma = r . (r ./ d) in sc[PCG_RHO]; p . q is
+// finished by pcg_alpha / pcg_alpha_ranks
+// *count += the rows whose d[i] is not positive (zero, negative or NaN)
+void eig_count_bad_diag(hipStream_t s, const double *d, int n, int *count);
+// p = r ./ d (first) or r ./ d + sc[BETA] p
+void eig_update_p(hipStream_t s, const double *r, const double *d, double *p, int n, const double *sc, int first);
+// q != null: r -= sc[ALPHA] q.  The partials of r . (r ./ d) from the r in registers, in
+// dot_partials' order
+void eig_update_r(hipStream_t s, double *r, const double *q, const double *d, int n, const double *sc,
+                  double *partials, int *nparts);
+// gamma' = sum(part): sc[BETA] = gamma' / sc[RHO] (0 where gamma = 0) into *ring_beta, sc[RHO] =
+// gamma' into *ring_gamma; first: gamma_0 (no beta).  _ranks: on the gathered rank values v
+void eig_gamma(hipStream_t s, const double *part, int np, double *sc, double *ring_beta, double *ring_gamma,
+               int first);
+void eig_gamma_ranks(hipStream_t s, const double *v, int nranks, double *sc, double *ring_beta,
+                     double *ring_gamma, int first);
 
 } // namespace amgk
 

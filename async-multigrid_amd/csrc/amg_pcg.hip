@@ -16,42 +16,6 @@
 
 namespace amgk {
 
-// sum of p[0..np) in sum_partials_k<<<1, 256>>>'s order (valid in thread 0)
-__device__ __forceinline__ double pcg_sum_partials(const double *__restrict__ p, int np, double *lds4)
-{
-   double s = 0.0;
-   for (int i = threadIdx.x; i < np; i += 256) s += p[i];
-   return block_sum_256(s, lds4);
-}
-
-// the quotient rule (one thread).  alpha = rho / pq (0 where pq = 0: a zero
-// right-hand side)
-__device__ __forceinline__ void pcg_alpha_q(double pq, double *__restrict__ sc, double *__restrict__ ring_alpha)
-{
-   const double alpha = pq != 0.0 ? sc[PCG_RHO] / pq : 0.0;
-   sc[PCG_PQ] = pq;
-   sc[PCG_ALPHA] = alpha;
-   if (ring_alpha) *ring_alpha = alpha;
-}
-
-// ||r|| = sqrt(rr) into *norm; rho' = rz; beta = rho' / rho (0 where rho = 0);
-// rho = rho'.  first: the start of a solve (rho only)
-__device__ __forceinline__ void pcg_beta_q(double rr, double rz, double *__restrict__ sc,
-                                           double *__restrict__ norm, double *__restrict__ ring_beta,
-                                           double *__restrict__ ring_rho, int first)
-{
-   *norm = sqrt(rr);
-   sc[PCG_RR] = rr;
-   if (!first) {
-      const double rho = sc[PCG_RHO];
-      const double beta = rho != 0.0 ? rz / rho : 0.0;
-      sc[PCG_BETA] = beta;
-      *ring_beta = beta;
-      *ring_rho = rz;
-   }
-   sc[PCG_RHO] = rz;
-}
-
 // pcg_alpha_q on pq = sum(part)
 __global__ __launch_bounds__(256) void pcg_alpha_k(const double *__restrict__ part, int np,
                                                    double *__restrict__ sc, double *__restrict__ ring_alpha)

@@ -13,6 +13,7 @@
 
 #include "amg_async.h"
 #include "amg_pcg.h"
+#include "amg_eig.h"
 
 int amg_reduce_to_host(amg_ctx *c, const double *partials, int np, int do_sqrt, double *out);
 int amg_hybrid_jgs_dev(amg_ctx *c, hipStream_t s, const amg_mat *A, const double *f, double *u,
@@ -1485,6 +1486,12 @@ extern "C" int amg_pcg_scalars(const amg_hier *H, double *alpha, double *beta, d
 {
    AMG_ARG(H && count && cap >= 0 && H->pcg.on, "amg_pcg_scalars: bad argument or no PCG state");
    return amg_cg::scalars(H->ctx->stream, H->pcg, alpha, beta, rho, cap, count);
+}
+
+extern "C" int amg_pcg_eigs(const amg_hier *H, double *eig_max, double *eig_min, int *iters)
+{
+   AMG_ARG(H && eig_max && eig_min && H->pcg.on, "amg_pcg_eigs: bad argument or no PCG state");
+   return amg_eig::pcg_extremes("amg_pcg_eigs", H->ctx->stream, H->pcg, eig_max, eig_min, iters);
 }
 
 extern "C" int amg_pcg_solve(amg_hier *H, const amg_vec *f, amg_vec *x, double *reshist, int *iters_done)

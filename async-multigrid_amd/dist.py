@@ -15,7 +15,7 @@ import threading
 
 import numpy as np
 
-from . import abi, check, lib, _dp, _ip, AmgError  # noqa: F401
+from . import abi, check, lib, _dp, _ip, _eigs_cg, AmgError  # noqa: F401
 
 OP_P2P, OP_ALLREDUCE, OP_ALLGATHER = 0, 1, 2
 
@@ -352,6 +352,18 @@ class DistHier:
         n = C.c_int()
         check(lib.amg_dist_pcg_scalars(self.h, _dp(a), _dp(b), _dp(r), int(cap), C.byref(n)))
         return a[:n.value], b[:n.value], r[:n.value]
+
+    def pcg_eigs(self):
+        """(emax, emin, k) of M^-1 A from the running PCG's scalars, the same on every rank (amg_dist_pcg_eigs)."""
+        emax, emin, k = C.c_double(), C.c_double(), C.c_int()
+        check(lib.amg_dist_pcg_eigs(self.h, C.byref(emax), C.byref(emin), C.byref(k)))
+        return emax.value, emin.value, k.value
+
+    def eigs_cg(self, iters=20, scale=1, r0_local=None):
+        """CG-Lanczos estimate on the distributed level-0 operator (amg_dist_eigs_cg; collective):
+        (emax, emin, alpha, beta, gamma, k), the same on every rank.  r0_local: this rank's rows of
+        the start vector (default: 2 u - 1 of the Lehmer stream by global row)."""
+        return _eigs_cg(lambda *a: lib.amg_dist_eigs_cg(self.h, *a), self.n0, iters, scale, r0_local)
 
     def async_solve(self, f_local):
         """Asynchronous additive solve (ASYNC_MULTADD / ASYNC_AFACX opts):

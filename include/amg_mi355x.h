@@ -570,6 +570,61 @@ int amg_pcg_get_x(amg_hier *H, amg_vec *x);
 /* alpha, beta and the new rho = r.z of the last *count = min(iterations done,
  * cap, 4096) iterations, oldest first (null arrays are skipped; host sync) */
 int amg_pcg_scalars(const amg_hier *H, double *alpha, double *beta, double *rho, int cap, int *count);
+/* the extreme eigenvalues of M^-1 A as the running PCG has seen them: amg_lanczos_extremes
+ * of the alpha / beta of its leading valid iterations (below; gamma_i is the rho iteration i
+ * started from), *iters their number.  A source for cheby_mu = (b + a) / (b - a) and
+ * cheby_delta = 2 / (b + a) (SMEM_Cheby.cpp:48-49; the DMEM driver's estimate is
+ * DMEM_Setup.cpp:77-87).  No kernel; host sync.  AMG_ERR_ARG before amg_pcg_start,
+ * AMG_ERR_UNSUPPORTED with no valid iteration or after more than 4096 iterations */
+int amg_pcg_eigs(const amg_hier *H, double *eig_max, double *eig_min, int *iters);
+/* ---- CG-Lanczos eigenvalue estimate (the role of hypre_ParCSRMaxEigEstimateCG(A_fine, 1,
+ * eig_CG_max_iters, ...) in DMEM_Setup.cpp:77-87, whose 1 / max_eig is the optimal Jacobi
+ * weight of -smoother j, async_j and async_sps) ----
+ * max_iter steps of conjugate gradients on A preconditioned by its diagonal d (scale 1; scale
+ * 0: d = 1, no division), without right-hand side or iterate, every statement one rounded fp64
+ * operation and every sum in amg_vec_dot's order:
+ *    gamma_0 = r . (r ./ d)
+ *    iteration i:  p = r ./ d (i = 0),  p = r ./ d + beta_{i-1} p (i > 0);  q = A p
+ *                  alpha_i = gamma_i / p.q  (0 where p.q = 0);  r -= alpha_i q
+ *                  gamma_{i+1} = r . (r ./ d);  beta_i = gamma_{i+1} / gamma_i  (0 where gamma_i = 0)
+ * In exact arithmetic these are the scalars of CG on D^-1/2 A D^-1/2 (no square root is taken
+ * on the device); hypre's own operation order and random start are not restated.  The scalars
+ * stay on the device and nothing is read back inside the loop.  Afterwards k = the number of
+ * leading iterations with gamma_i >= DBL_EPSILON (hypre's break) and alpha_i finite and
+ * positive is returned in *iters, and eig_max / eig_min = amg_lanczos_extremes of those k.
+ * alpha / beta / gamma (each may be NULL): the whole history, max_iter / max_iter /
+ * max_iter + 1 entries.  r0: the start vector (host, A's rows), or NULL for 2 u_g - 1 with u
+ * = amg_lehmer_stream(1, 0, n).  A: any registered square matrix, in whatever storage form
+ * it has.  max_iter in [1, 4096].  scale 1 with a row whose a_ii <= 0: AMG_ERR_ARG before any
+ * iteration; k = 0: AMG_ERR_UNSUPPORTED (the histories are still returned).  Host sync. */
+int amg_eigs_cg(amg_ctx *ctx, const amg_mat *A, int scale, int max_iter, const double *r0, double *eig_max,
+                double *eig_min, double *alpha, double *beta, double *gamma, int *iters);
+/* The Lanczos tridiagonal of k CG iterations and its extreme eigenvalues (host only; the
+ * estimate DMEM_Setup.cpp:77-87 takes from hypre, which calls EISPACK tql1 instead).
+ * alpha[0..k), beta[0..k) in amg_pcg_scalars' convention: beta[j] is formed at the end of
+ * iteration j (beta[k-1] is not read).  Each step one rounded fp64 operation, sqrt the
+ * host's:
+ *    tridiag[0] = 1 / alpha[0];  trioffd[0] = 0
+ *    tridiag[i] = (1 / alpha[i-1]) * beta[i-1] + 1 / alpha[i]
+ *    trioffd[i] = (1 / alpha[i-1]) * sqrt(beta[i-1])                      (i >= 1)
+ * Sturm-sequence bisection inside the Gershgorin interval: with rad_i = |trioffd[i]| +
+ * |trioffd[i+1]| (trioffd[k] = 0), lo = min_i (tridiag[i] - rad_i), hi = max_i (tridiag[i] +
+ * rad_i).  count(x), the eigenvalues below x:
+ *    q = tridiag[0] - x;  q = (tridiag[i] - x) - (trioffd[i] * trioffd[i]) / q   (i >= 1)
+ * where a q that is exactly 0 is replaced by -DBL_MIN as soon as it is formed, and every
+ * q < 0 counts one.  From l = lo, h = hi: m = 0.5 * (l + h); while l < m and m < h, the
+ * side named below becomes m and m is formed again.
+ *    eig_max: h = m where count(m) == k, else l = m; the result is h (an upper end)
+ *    eig_min: h = m where count(m) >= 1, else l = m; the result is l (a lower end)
+ * k < 1: AMG_ERR_UNSUPPORTED.  An alpha that is 0 or not finite, or a beta[j < k-1] that is
+ * negative or not finite: AMG_ERR_ARG.  tridiag / trioffd hold k entries. */
+int amg_lanczos_extremes(int k, const double *alpha, const double *beta, double *tridiag, double *trioffd,
+                         double *eig_max, double *eig_min);
+/* out[j] = w_{skip + j + 1} / 2147483647.0 of the Lehmer stream w_0 = seed, w <- 16807 w mod
+ * (2^31 - 1); the skip is taken by 16807^skip mod (2^31 - 1), so a rank forms its rows of
+ * a stream indexed by the global row (the default start vector of the estimates that stand in
+ * for DMEM_Setup.cpp:77-87's; host only).  seed in [1, 2^31 - 2] */
+int amg_lehmer_stream(long long seed, long long skip, long long n, double *out);
 /* profile: accumulated device milliseconds and launch counts of the fine-level
 s * kernels since the last reset: [0] level-0 residual in the cycle, [1] level-0
  * smoother sweeps, [2] R_0 restriction, [3] P_0 prolongation, [4] outer residual
@@ -823,6 +878,21 @@ int amg_dist_pcg_scalars(const amg_dist_hier *D, double *alpha, double *beta, do
  * reshist[k] / reshist[0] < tol, on every rank at the same k (DMEM_Main.cpp:788-804) */
 int amg_dist_pcg_solve(amg_dist_hier *D, const double *f_local, double *x_local, double *reshist,
                        int *iters_done);
+/* as amg_pcg_eigs, from the distributed PCG's scalars: the same bits on every rank
+ * (a source of cheby_mu / cheby_delta for accel_type, SMEM_Cheby.cpp:48-49; the DMEM
+ * driver's estimate is DMEM_Setup.cpp:77-87).  Not collective */
+int amg_dist_pcg_eigs(const amg_dist_hier *D, double *eig_max, double *eig_min, int *iters);
+/* amg_eigs_cg on the distributed level-0 operator of either form, over either transport
+ * (DMEM_Setup.cpp:77-87: hypre_ParCSRMaxEigEstimateCG on the rank-partitioned A_fine).
+ * q = A p is the distributed product; the two dot products of an iteration are gathered as
+ * amg_dist_pcg_*'s are, so every rank returns the same bits, they depend on the row
+ * partition only, and one rank gives the bits of amg_eigs_cg.  r0_local: this rank's rows
+ * of the start vector, or NULL for 2 u_g - 1 by global row g (amg_lehmer_stream(1, row0,
+ * n)): the default does not depend on the partition.  Collective; no hierarchy option is
+ * read and no solve's state is touched.  With scale 1 the ranks' counts of rows with a_ii
+ * <= 0 are gathered first, so every rank returns AMG_ERR_ARG together. */
+int amg_dist_eigs_cg(amg_dist_hier *D, int scale, int max_iter, const double *r0_local, double *eig_max,
+                     double *eig_min, double *alpha, double *beta, double *gamma, int *iters);
 /* asynchronous additive AMG across GPUs (DMEM_Add DMEM_Add.cpp:20-178, AddCycle
  * :180-329, DMEM_AddCorrect_LocalRes :391-458; SMEM_Async_Add_AMG semantics):
  * hierarchy created with solver ASYNC_MULTADD or ASYNC_AFACX.  Every level runs
