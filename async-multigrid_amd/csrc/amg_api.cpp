@@ -263,7 +263,7 @@ int amg_ctx_partials(amg_ctx *c, size_t n, double **out)
 // ---------------------------------------------------------------------------
 static int mat_alloc(amg_ctx *c, int nrows, int ncols, long long nnz, amg_mat **out)
 {
-   amg_mat *A = new amg_mat();
+   amg_mat_ptr A(new amg_mat());
    A->ctx = c;
    A->nrows = nrows;
    A->ncols = ncols;
@@ -273,645 +273,13 @@ static int mat_alloc(amg_ctx *c, int nrows, int ncols, long long nnz, amg_mat **
    if (e == hipSuccess) e = hipMalloc(&A->col, np * sizeof(int));
    if (e == hipSuccess) e = hipMalloc(&A->val, np * sizeof(double));
    if (e == hipSuccess) e = hipMalloc(&A->diag, std::max(1, nrows) * sizeof(double));
-   if (e != hipSuccess) {
-      hipFree(A->rowptr); hipFree(A->col); hipFree(A->val); hipFree(A->diag);
-      delete A;
+   if (e != hipSuccess)
       return amg_set_error(AMG_ERR_OOM, "amg_csr_register: device allocation of %lld nnz failed: %s",
                            nnz, hipGetErrorString(e));
-   }
    // padding: col 0 (a valid x index), val 0
    AMG_HIP(hipMemsetAsync(A->col + nnz, 0, AMG_NNZ_PAD * sizeof(int), c->stream));
    AMG_HIP(hipMemsetAsync(A->val + nnz, 0, AMG_NNZ_PAD * sizeof(double), c->stream));
-   *out = A;
-   return AMG_OK;
-}
-
-// value-indexed CSR (CSR-VI): when the matrix holds at most 256 distinct
-// values (by bit pattern) the hot kernels stream one byte per entry instead
-// of eight and read the value from an LDS table -- bit-identical products.
-// val stays resident for the other kernels and for amg_mat_download.
-static int build_value_index(amg_mat *A)
-{
-   amg_ctx *c = A->ctx;
-   hipStream_t s = c->stream;
-   constexpr int NS = 4096;
-   unsigned long long *slots = nullptr;
-   AMG_HIP(hipMalloc(&slots, NS * sizeof(unsigned long long) + 64));
-   int *count = reinterpret_cast<int *>(slots + NS);
-   AMG_HIP(hipMemsetAsync(slots, 0xff, NS * sizeof(unsigned long long), s));
-   AMG_HIP(hipMemsetAsync(count, 0, sizeof(int), s));
-   amgk::vi_collect(s, A->val, A->nnz, slots, NS, count);
-   std::vector<unsigned long long> h(NS);
-   int cnt = 0;
-   AMG_HIP(hipMemcpyAsync(h.data(), slots, NS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(&cnt, count, sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   if (cnt < 1 || cnt > 256) {
-      hipFree(slots);
-      return AMG_OK; // plain CSR
-   }
-   std::vector<unsigned long long> keys;
-   for (auto k : h)
-      if (k != ~0ULL) keys.push_back(k);
-   std::sort(keys.begin(), keys.end());
-   const int T = (int)keys.size();
-   std::vector<double> tab(256, 0.0);
-   std::memcpy(tab.data(), keys.data(), T * sizeof(double));
-   hipError_t e = hipMalloc(&A->vidx, (size_t)A->nnz + 64);
-   if (e == hipSuccess) e = hipMalloc(&A->vtab, 256 * sizeof(double));
-   if (e != hipSuccess) { // not enough room: keep plain CSR
-      hipFree(A->vidx);
-      hipFree(A->vtab);
-      A->vidx = nullptr;
-      A->vtab = nullptr;
-      hipFree(slots);
-      (void)hipGetLastError();
-      return AMG_OK;
-   }
-   AMG_HIP(hipMemcpyAsync(slots, keys.data(), T * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->vtab, tab.data(), 256 * sizeof(double), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemsetAsync(A->vidx + A->nnz, 0, 64, s));
-   amgk::vi_encode(s, A->val, A->nnz, slots, T, A->vidx);
-   AMG_HIP(hipStreamSynchronize(s));
-   hipFree(slots);
-   A->vi_n = T;
-   return AMG_OK;
-}
-
-// dictionary-coded CSR (CSR-DC) on top of the value index: when every entry's
-// (col - row, value) pair comes from at most 256 distinct pairs and no row
-// holds more than AMG_DC_MAXROW entries, each entry becomes one byte and the
-// lane-per-row kernel reads x[row + off] coalesced across a wave.
-static int build_dict_index(amg_mat *A)
-{
-   amg_ctx *c = A->ctx;
-   hipStream_t s = c->stream;
-   constexpr int NS = 4096;
-   unsigned long long *slots = nullptr;
-   AMG_HIP(hipMalloc(&slots, NS * sizeof(unsigned long long) + 64));
-   int *count = reinterpret_cast<int *>(slots + NS);
-   AMG_HIP(hipMemsetAsync(slots, 0xff, NS * sizeof(unsigned long long), s));
-   AMG_HIP(hipMemsetAsync(count, 0, 3 * sizeof(int), s));
-   amgk::dc_collect(s, A, slots, NS, count, count + 1);
-   std::vector<unsigned long long> h(NS);
-   int cm[3] = {0, 0, 0}; // distinct pairs, longest row, some anchor != row
-   AMG_HIP(hipMemcpyAsync(h.data(), slots, NS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(cm, count, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   if (cm[0] < 1 || cm[0] > 256 || cm[1] > AMG_DC_MAXROW) {
-      hipFree(slots);
-      return AMG_OK;
-   }
-   std::vector<unsigned long long> keys;
-   for (auto k : h)
-      if (k != ~0ULL) keys.push_back(k);
-   std::sort(keys.begin(), keys.end());
-   const int T = (int)keys.size();
-   std::vector<double> vt(256, 0.0);
-   AMG_HIP(hipMemcpy(vt.data(), A->vtab, 256 * sizeof(double), hipMemcpyDeviceToHost));
-   std::vector<int> off(256, 0);
-   std::vector<double> dv(256, 0.0);
-   for (int t = 0; t < T; t++) {
-      off[t] = (int)(unsigned int)(keys[t] >> 8);
-      dv[t] = vt[keys[t] & 0xff];
-   }
-   // anchors only where some row does not start at its own index (the
-   // transfers); a distributed slab [owned | ghost] keeps anchor = row
-   const bool need_anchor = cm[2] != 0;
-   hipError_t e = hipMalloc(&A->didx, (size_t)A->nnz + 64);
-   if (e == hipSuccess) e = hipMalloc(&A->doff, 256 * sizeof(int));
-   if (e == hipSuccess) e = hipMalloc(&A->dval, 256 * sizeof(double));
-   if (e == hipSuccess && need_anchor) e = hipMalloc(&A->danch, std::max(1, A->nrows) * sizeof(int));
-   if (e != hipSuccess) {
-      hipFree(A->didx);
-      hipFree(A->doff);
-      hipFree(A->dval);
-      hipFree(A->danch);
-      A->didx = nullptr;
-      A->doff = nullptr;
-      A->dval = nullptr;
-      A->danch = nullptr;
-      hipFree(slots);
-      (void)hipGetLastError();
-      return AMG_OK;
-   }
-   AMG_HIP(hipMemcpyAsync(slots, keys.data(), T * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->doff, off.data(), 256 * sizeof(int), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->dval, dv.data(), 256 * sizeof(double), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemsetAsync(A->didx + A->nnz, 0, 64, s));
-   amgk::dc_encode(s, A, slots, T, A->didx, A->danch);
-   AMG_HIP(hipStreamSynchronize(s));
-   hipFree(slots);
-   A->dc_n = T;
-   A->dc_maxrow = cm[1];
-   return AMG_OK;
-}
-
-// row-pattern-coded CSR: when every row is non-empty and the rows' dictionary
-// sequences take at most 256 distinct values, one byte per row names the
-// sequence.  Lossless: the kernels walk the same entries in
-// the same order.
-static int build_row_pattern(amg_mat *A)
-{
-   amg_ctx *c = A->ctx;
-   hipStream_t s = c->stream;
-   constexpr int NS = 4096;
-   unsigned long long *slots = nullptr;
-   AMG_HIP(hipMalloc(&slots, NS * sizeof(unsigned long long) + NS * sizeof(int) + 64));
-   int *rep = reinterpret_cast<int *>(slots + NS);
-   int *count = rep + NS;
-   AMG_HIP(hipMemsetAsync(slots, 0xff, NS * sizeof(unsigned long long), s));
-   AMG_HIP(hipMemsetAsync(count, 0, 2 * sizeof(int), s));
-   amgk::rp_collect(s, A, slots, rep, NS, count, count + 1);
-   std::vector<unsigned long long> h(NS);
-   std::vector<int> hr(NS);
-   int cb[2] = {0, 0}; // distinct row sequences, rows that cannot be coded
-   AMG_HIP(hipMemcpyAsync(h.data(), slots, NS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(hr.data(), rep, NS * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(cb, count, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   if (cb[0] < 1 || cb[0] > 256 || cb[1] != 0) {
-      hipFree(slots);
-      return AMG_OK;
-   }
-   std::vector<std::pair<unsigned long long, int>> kr;
-   for (int i = 0; i < NS; i++)
-      if (h[i] != ~0ULL) kr.push_back({h[i], hr[i]});
-   std::sort(kr.begin(), kr.end());
-   const int T = (int)kr.size();
-   std::vector<unsigned long long> keys(T);
-   std::vector<int> reps(T);
-   for (int t = 0; t < T; t++) {
-      keys[t] = kr[t].first;
-      reps[t] = kr[t].second;
-   }
-   hipError_t e = hipMalloc(&A->rpat, std::max(1, A->nrows));
-   if (e == hipSuccess) e = hipMalloc(&A->ptab, 256 * AMG_RP_STRIDE);
-   if (e != hipSuccess) {
-      hipFree(A->rpat);
-      hipFree(A->ptab);
-      A->rpat = A->ptab = nullptr;
-      hipFree(slots);
-      (void)hipGetLastError();
-      return AMG_OK;
-   }
-   AMG_HIP(hipMemsetAsync(A->ptab, 0, 256 * AMG_RP_STRIDE, s));
-   AMG_HIP(hipMemcpyAsync(slots, keys.data(), T * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(rep, reps.data(), T * sizeof(int), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemsetAsync(count + 1, 0, sizeof(int), s));
-   amgk::rp_table(s, A, rep, T, A->ptab);
-   amgk::rp_encode(s, A, slots, T, A->ptab, A->rpat, count + 1);
-   AMG_HIP(hipMemcpyAsync(cb, count, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   hipFree(slots);
-   if (cb[1] != 0) { // a hash collision: keep the dictionary-coded form
-      hipFree(A->rpat);
-      hipFree(A->ptab);
-      A->rpat = A->ptab = nullptr;
-      return AMG_OK;
-   }
-   A->rp_n = T;
-   return AMG_OK;
-}
-
-// paired-row-pattern CSR on top of the row patterns: rows 2t and 2t+1 share
-// one merged entry list in which an entry of row 2t at column c and an entry
-// of row 2t+1 at column c + 1 are one 16-byte x load.
-// Columns are relative to row 2t's anchor (the row itself for square
-// diagonal-first operators); row 2t+1's anchor is da further.  The merge is a
-// shortest common supersequence of the two rows' entry lists (matched on
-// column), so each row still sums its own entries in its CSR order:
-// bit-identical to the single-row kernel.
-static void pair_merge(const unsigned char *a, int la, const unsigned char *b, int lb, int da,
-                       const std::vector<int> &off, std::vector<unsigned int> &out)
-{
-   int dp[AMG_PP_MAXROW + 2][AMG_PP_MAXROW + 2] = {};
-   auto match = [&](int i, int j) { return off[b[j]] + da == off[a[i]] + 1; };
-   for (int i = la - 1; i >= 0; i--)
-      for (int j = lb - 1; j >= 0; j--)
-         dp[i][j] = match(i, j) ? dp[i + 1][j + 1] + 1 : std::max(dp[i + 1][j], dp[i][j + 1]);
-   int i = 0, j = 0;
-   while (i < la || j < lb) {
-      if (i < la && j < lb && match(i, j) && dp[i][j] == dp[i + 1][j + 1] + 1) {
-         out.push_back(a[i] | (unsigned)b[j] << 8 | 3u << 16);
-         i++;
-         j++;
-      } else if (j >= lb || (i < la && dp[i + 1][j] >= dp[i][j + 1])) {
-         out.push_back(a[i] | 1u << 16);
-         i++;
-      } else {
-         out.push_back((unsigned)b[j] << 8 | 2u << 16);
-         j++;
-      }
-   }
-}
-
-// Slab-compressed anchors for the paired kernel (amg_internal.h): anchor(2t)
-// = pbase[2t >> 9] + pdelta[t].  Kept only when every 512-row slab's anchors
-// span at most 65535 (interpolation: a fine line maps to half a coarse line).
-static int compress_pair_anchors(amg_mat *A)
-{
-   hipStream_t s = A->ctx->stream;
-   const size_t ns = ((size_t)A->nrows + 511) / 512, np = ((size_t)A->nrows + 1) / 2;
-   int *ok = nullptr;
-   hipError_t e = hipMalloc(&A->pbase, ns * sizeof(int));
-   if (e == hipSuccess) e = hipMalloc(&A->pdelta, np * sizeof(unsigned short));
-   if (e == hipSuccess) e = hipMalloc(&ok, sizeof(int));
-   int okh = 0;
-   if (e == hipSuccess) {
-      const int one = 1;
-      AMG_HIP(hipMemcpyAsync(ok, &one, sizeof(int), hipMemcpyHostToDevice, s));
-      amgk::pp_anchor_compress(s, A, A->pbase, A->pdelta, ok);
-      AMG_HIP(hipMemcpyAsync(&okh, ok, sizeof(int), hipMemcpyDeviceToHost, s));
-      AMG_HIP(hipStreamSynchronize(s));
-   }
-   hipFree(ok);
-   if (e != hipSuccess || !okh) {
-      hipFree(A->pbase);
-      hipFree(A->pdelta);
-      A->pbase = nullptr;
-      A->pdelta = nullptr;
-      (void)hipGetLastError();
-   }
-   return AMG_OK;
-}
-
-static int build_pair_pattern(amg_mat *A)
-{
-   amg_ctx *c = A->ctx;
-   hipStream_t s = c->stream;
-   constexpr int NK = AMG_PP_NK;
-   unsigned char *flags = nullptr;
-   AMG_HIP(hipMalloc(&flags, 2 * (size_t)NK + 1 + 256 * sizeof(unsigned long long) + 8));
-   unsigned char *map = flags + NK + 1;
-   unsigned long long *counts = reinterpret_cast<unsigned long long *>(
-      (reinterpret_cast<uintptr_t>(map + NK) + 7) & ~(uintptr_t)7);
-   AMG_HIP(hipMemsetAsync(flags, 0, NK + 1, s));
-   amgk::pp_collect(s, A, flags);
-   std::vector<unsigned char> hf(NK + 1), pt(256 * AMG_RP_STRIDE);
-   std::vector<int> off(256);
-   AMG_HIP(hipMemcpyAsync(hf.data(), flags, NK + 1, hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(pt.data(), A->ptab, pt.size(), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(off.data(), A->doff, 256 * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   std::vector<unsigned char> hm(NK, 0);
-   std::vector<unsigned int> tab;
-   const int PS = amg_pp_stride(A->dc_maxrow);
-   int T = hf[NK] ? 257 : 0; // an anchor delta out of range: not pair-coded
-   bool centre0 = !A->danch; // square diagonal-first: is entry 0 the diagonal of both rows?
-   std::vector<int> msz(256, 0), ssz(256, 0); // per pattern: merged entries, the longer row's
-   for (int k = 0; k < NK && T <= 256; k++) {
-      if (!hf[k]) continue;
-      if (T == 256) {
-         T++;
-         break;
-      }
-      const int pk = k / AMG_PP_NDA, da = k % AMG_PP_NDA - AMG_PP_DA0;
-      const int p0 = pk / 257, p1 = pk % 257;
-      const unsigned char *a = pt.data() + p0 * AMG_RP_STRIDE;
-      std::vector<unsigned int> el;
-      if (p1 < 256) {
-         const unsigned char *b = pt.data() + p1 * AMG_RP_STRIDE;
-         pair_merge(a + 1, a[0], b + 1, b[0], A->danch ? da : 1, off, el);
-         msz[T] = (int)el.size();
-         ssz[T] = std::max<int>(a[0], b[0]);
-      } else {
-         for (int j = 0; j < a[0]; j++) el.push_back(a[1 + j] | 1u << 16);
-      }
-      // header: nel | first dictionary entry of row 2t << 8 | of row 2t+1 << 16
-      // | row 2t+1 present << 24 | (anchor delta + 16) << 25
-      std::vector<unsigned int> w(PS, 0);
-      w[0] = (unsigned)el.size() | (unsigned)a[1] << 8 |
-             (p1 < 256 ? (unsigned)pt[p1 * AMG_RP_STRIDE + 1] << 16 | 1u << 24 : 0u) |
-             (unsigned)(da + 16) << 25;
-      for (size_t e = 0; e < el.size(); e++) w[1 + e] = el[e];
-      centre0 = centre0 && !el.empty() && off[el[0] & 0xff] == 0 && (el[0] >> 16 & 1) &&
-                (p1 == 256 || (el[0] >> 16 & 3) == 3);
-      tab.insert(tab.end(), w.begin(), w.end());
-      hm[k] = (unsigned char)T++;
-   }
-   if (T < 1 || T > 256 || (size_t)T * PS * 4 > (size_t)AMG_PP_LDS) {
-      hipFree(flags);
-      return AMG_OK;
-   }
-   const size_t np = ((size_t)A->nrows + 1) / 2;
-   hipError_t e = hipMalloc(&A->ppat, std::max<size_t>(1, np));
-   if (e == hipSuccess) e = hipMalloc(&A->pptab, tab.size() * sizeof(unsigned int));
-   if (e != hipSuccess) {
-      hipFree(A->ppat);
-      hipFree(A->pptab);
-      A->ppat = nullptr;
-      A->pptab = nullptr;
-      hipFree(flags);
-      (void)hipGetLastError();
-      return AMG_OK;
-   }
-   AMG_HIP(hipMemcpyAsync(map, hm.data(), NK, hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->pptab, tab.data(), tab.size() * sizeof(unsigned int), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemsetAsync(counts, 0, 256 * sizeof(unsigned long long), s));
-   amgk::pp_encode(s, A, map, A->ppat, counts);
-   std::vector<unsigned long long> cnt(256);
-   AMG_HIP(hipMemcpyAsync(cnt.data(), counts, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   hipFree(flags);
-   // a pair lane walks the merged list: worth it only when it is hardly
-   // longer than the longer of its rows, counted over all row pairs (7-pt /
-   // 27-pt operators and interpolation: as long; restriction, anchors 2
-   // apart: 4/3 as long, and slower than one row per lane)
-   double merged = 0.0, single = 0.0;
-   for (int t = 0; t < T; t++) {
-      merged += (double)cnt[t] * msz[t];
-      single += (double)cnt[t] * ssz[t];
-   }
-   if (merged > AMG_PP_MAXFILL * single) {
-      hipFree(A->ppat);
-      hipFree(A->pptab);
-      A->ppat = nullptr;
-      A->pptab = nullptr;
-      return AMG_OK;
-   }
-   A->pp_n = T;
-   A->pp_stride = PS;
-   A->pp_centre0 = centre0 ? 1 : 0;
-   if (A->ctx->pair_anchor16 && A->danch && A->nrows > 0) AMG_TRY(compress_pair_anchors(A));
-   return AMG_OK;
-}
-
-// Master-pattern form on top of the pair patterns of a square,
-// diagonal-first operator: every row's column offsets (relative to the row)
-// must follow the master order -- 0 first, then ascending -- so a row's
-// entries are an ordered subsequence of the master list and walking the
-// master with per-row use bits adds exactly the row's products in its CSR
-// order (bit-identical).  Offsets then become wave-uniform scalars and the
-// per-entry LDS lookups of the pair kernel disappear.
-static int build_master_pattern(amg_mat *A)
-{
-   if (!A->ppat || A->danch || A->nrows != A->ncols || A->nrows < 2 || A->pp_n < 1) return AMG_OK;
-   hipStream_t s = A->ctx->stream;
-   const int T = A->pp_n, PS = A->pp_stride, D = A->dc_n;
-   std::vector<unsigned int> tab((size_t)T * PS);
-   std::vector<int> off(256);
-   std::vector<double> val(256);
-   AMG_HIP(hipMemcpyAsync(tab.data(), A->pptab, tab.size() * 4, hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(off.data(), A->doff, 256 * sizeof(int), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipMemcpyAsync(val.data(), A->dval, 256 * sizeof(double), hipMemcpyDeviceToHost, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   std::vector<int> mo;
-   for (int d = 0; d < D; d++) mo.push_back(off[d]);
-   std::sort(mo.begin(), mo.end());
-   mo.erase(std::unique(mo.begin(), mo.end()), mo.end());
-   auto z = std::find(mo.begin(), mo.end(), 0);
-   if (z == mo.end() || (int)mo.size() > AMG_MP_MAXJ) return AMG_OK;
-   mo.erase(z);
-   mo.insert(mo.begin(), 0);
-   const int J = (int)mo.size();
-   auto pos = [&](int o) { return (int)(std::find(mo.begin(), mo.end(), o) - mo.begin()); };
-   std::vector<unsigned long long> mask(T, 0);
-   std::vector<double> mv((size_t)T * J * 2, 0.0);
-   std::vector<unsigned long long> uni_bits(J, 0);
-   std::vector<int> uni_set(J, 0);
-   bool uni = true;
-   for (int t = 0; t < T; t++) {
-      const unsigned int *w = tab.data() + (size_t)t * PS;
-      const int nel = w[0] & 0xff;
-      const bool two = (w[0] >> 24) & 1;
-      int last[2] = {-1, -1};
-      for (int e = 0; e < nel; e++) {
-         const unsigned int en = w[1 + e];
-         for (int r = 0; r < 2; r++) {
-            if (!(en >> (16 + r) & 1)) continue;
-            const int d = r ? (en >> 8 & 0xff) : (en & 0xff);
-            const int j = pos(off[d]);
-            if (j <= last[r]) return AMG_OK; // not an ordered subsequence of the master
-            last[r] = j;
-            mask[t] |= 1ULL << (2 * j + r);
-            mv[((size_t)t * J + j) * 2 + r] = val[d];
-            unsigned long long bits;
-            std::memcpy(&bits, &val[d], 8);
-            if (!uni_set[j]) {
-               uni_set[j] = 1;
-               uni_bits[j] = bits;
-            } else if (uni_bits[j] != bits) {
-               uni = false;
-            }
-         }
-      }
-      // a_ii = A_data[A_i[i]] and x_i come from master entry 0 (the diagonal)
-      if (!(mask[t] & 1ULL) || (two && !(mask[t] & 2ULL))) return AMG_OK;
-   }
-   if (!uni && (size_t)T * J * 16 > (size_t)AMG_MP_LDS) return AMG_OK;
-   hipError_t e = hipMalloc(&A->mpmask, (size_t)T * 8);
-   if (e == hipSuccess && !uni) e = hipMalloc(&A->mpval, mv.size() * 8);
-   if (e != hipSuccess) {
-      hipFree(A->mpmask);
-      hipFree(A->mpval);
-      A->mpmask = nullptr;
-      A->mpval = nullptr;
-      (void)hipGetLastError();
-      return AMG_OK;
-   }
-   AMG_HIP(hipMemcpyAsync(A->mpmask, mask.data(), (size_t)T * 8, hipMemcpyHostToDevice, s));
-   if (!uni) AMG_HIP(hipMemcpyAsync(A->mpval, mv.data(), mv.size() * 8, hipMemcpyHostToDevice, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   for (int j = 0; j < J; j++) {
-      A->mp_off[j] = mo[j];
-      std::memcpy(&A->mp_val[j], &uni_bits[j], 8);
-   }
-   A->mp_uni = uni ? 1 : 0;
-   A->mp_J = J;
-   // plane-marching form: master [0, -P, -S, -1, +1, +S, +P], whole planes of
-   // P rows (P % 512 == 0: a workgroup's 512 positions never straddle planes)
-   // (S even: every pair's +-S operand pair is one aligned-in-range 16-byte load)
-   if (A->ctx->plane_march && J == 7 && mo[3] == -1 && mo[4] == 1 && mo[1] == -mo[6] &&
-       mo[2] == -mo[5] && mo[5] > 1 && mo[5] % 2 == 0 && mo[6] > mo[5] && mo[6] % 512 == 0 &&
-       A->nrows % mo[6] == 0 && A->nrows / mo[6] >= 2 && A->nrows < (1 << 29)) { // 32-bit byte offsets
-      A->mz_P = mo[6];
-      A->mz_S = mo[5];
-   }
-   // 27-pt plane march: master [0, dz P + dy S + dx ascending (centre skipped)]
-   if (A->ctx->plane_march && J == 27 && A->nrows < (1 << 29) && (uni || T <= 64)) {
-      const int S = mo[16], P = mo[22];
-      bool ok = S >= 4 && S % 2 == 0 && P % 512 == 0 && P % S == 0 && P / S >= 3 && A->nrows % P == 0 &&
-                A->nrows / P >= 2;
-      for (int L = 0, j = 1; ok && L < 27; L++) {
-         if (L == 13) continue;
-         const int o = (L / 9 - 1) * P + ((L / 3) % 3 - 1) * S + (L % 3 - 1);
-         ok = mo[j++] == o;
-      }
-      int dom = -1;
-      if (ok && !uni) {
-         // the most frequent pattern using all 27 entries in both rows with
-         // bit-equal values in the two rows
-         std::vector<unsigned char> pp((size_t)(A->nrows / 2));
-         AMG_HIP(hipMemcpy(pp.data(), A->ppat, pp.size(), hipMemcpyDeviceToHost));
-         std::vector<long long> cnt(T, 0);
-         for (unsigned char q : pp) cnt[q]++;
-         const unsigned long long full = (1ull << 54) - 1;
-         for (int t = 0; t < T; t++) {
-            if (mask[t] != full) continue;
-            bool same = true;
-            for (int j = 0; j < J && same; j++)
-               same = std::memcmp(&mv[((size_t)t * J + j) * 2], &mv[((size_t)t * J + j) * 2 + 1], 8) == 0;
-            if (same && (dom < 0 || cnt[t] > cnt[dom])) dom = t;
-         }
-         if (dom >= 0)
-            for (int j = 0; j < J; j++) A->mz_domval[j] = mv[((size_t)dom * J + j) * 2];
-         // x-edge pair patterns (the waves at both ends of every line)
-         if (dom >= 0) {
-            unsigned long long lo_x = 0, hi_y = 0; // row 2t's mask without dx = -1, row 2t+1's without +1
-            for (int j = 0; j < 27; j++) {
-               const int L = j == 0 ? 13 : (j <= 13 ? j - 1 : j), dx = L % 3 - 1;
-               if (dx != -1) lo_x |= 1ull << (2 * j);
-               if (dx != 1) hi_y |= 2ull << (2 * j);
-            }
-            const unsigned long long even = 0x5555555555555555ull & full, odd = 0xAAAAAAAAAAAAAAAAull & full;
-            long long best_lo = 0, best_hi = 0;
-            for (int t = 0; t < T; t++) {
-               auto same = [&](int j, int r) {
-                  return std::memcmp(&mv[((size_t)t * J + j) * 2 + r], &A->mz_domval[j], 8) == 0;
-               };
-               if (mask[t] == (lo_x | odd) && cnt[t] > best_lo) {
-                  bool ok = true;
-                  for (int j = 0; j < J && ok; j++) ok = same(j, 1) && (!((lo_x >> (2 * j)) & 1) || same(j, 0));
-                  if (ok) A->mz_xlo = t, best_lo = cnt[t];
-               }
-               if (mask[t] == (even | hi_y) && cnt[t] > best_hi) {
-                  bool ok = true;
-                  for (int j = 0; j < J && ok; j++) ok = same(j, 0);
-                  if (ok) {
-                     A->mz_xhi = t, best_hi = cnt[t];
-                     for (int j = 0; j < J; j++) A->mz_hival[j] = mv[((size_t)t * J + j) * 2 + 1];
-                  }
-               }
-            }
-         }
-      }
-      if (ok) {
-         A->mz_P = P;
-         A->mz_S = S;
-         A->mz27 = 1;
-         A->mz_dom = dom;
-      }
-   }
-   return AMG_OK;
-}
-
-// back to the row-pattern form (pair / master / march forms dropped)
-static void drop_pair_forms(amg_mat *A)
-{
-   hipFree(A->ppat);
-   hipFree(A->pptab);
-   hipFree(A->mpmask);
-   hipFree(A->mpval);
-   A->ppat = nullptr;
-   A->pptab = nullptr;
-   A->mpmask = nullptr;
-   A->mpval = nullptr;
-   A->pp_n = A->pp_stride = A->pp_centre0 = 0;
-   A->mp_J = A->mp_uni = 0;
-   A->mz_P = A->mz_S = A->mz27 = 0;
-   A->mz_dom = -1;
-   A->mz_xlo = A->mz_xhi = -1;
-}
-
-int amg_mat_finish(amg_mat *A)
-{
-   amgk::extract_diag(A->ctx->stream, A);
-   AMG_HIP(hipGetLastError());
-   {
-      int *d = nullptr;
-      AMG_HIP(hipMalloc(&d, 2 * sizeof(int)));
-      AMG_HIP(hipMemsetAsync(d, 0, 2 * sizeof(int), A->ctx->stream));
-      amgk::row_max(A->ctx->stream, A, d);
-      amgk::diag_uniform(A->ctx->stream, A, d + 1);
-      int h[2] = {0, 0};
-      double d0 = 0.0;
-      hipError_t e = hipMemcpyAsync(h, d, 2 * sizeof(int), hipMemcpyDeviceToHost, A->ctx->stream);
-      if (e == hipSuccess && A->nrows > 0)
-         e = hipMemcpyAsync(&d0, A->diag, sizeof(double), hipMemcpyDeviceToHost, A->ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(A->ctx->stream);
-      hipFree(d);
-      if (e != hipSuccess) return amg_set_error(AMG_ERR_HIP, "amg_mat_finish: %s", hipGetErrorString(e));
-      A->maxrow = h[0];
-      A->diag_uni = A->nrows > 0 && h[1] == 0;
-      A->diag_u = d0;
-   }
-   if (A->ctx->value_index && A->nnz > 0) AMG_TRY(build_value_index(A));
-   if (A->ctx->dict_index && A->vidx) AMG_TRY(build_dict_index(A));
-   if (A->ctx->row_pattern && A->didx) AMG_TRY(build_row_pattern(A));
-   const bool pp = A->dc_maxrow <= 8 || A->nrows >= AMG_PP_LONG_MIN_ROWS || A->ctx->pair_pattern == 2;
-   // long-row operators below the pair-coding size still try the 27-pt march
-   // (kept only if it applies: the pair kernel itself is slower there)
-   const bool try27 = !pp && A->ctx->plane_march && A->ctx->master_pattern;
-   if (A->ctx->pair_pattern && A->rpat && A->dc_maxrow <= AMG_PP_MAXROW && (pp || try27))
-      AMG_TRY(build_pair_pattern(A));
-   if (A->ctx->master_pattern && A->ppat) AMG_TRY(build_master_pattern(A));
-   if (try27 && A->ppat && !A->mz27 && !A->pbase) drop_pair_forms(A);
-   return AMG_OK;
-}
-
-extern "C" int amg_set_row_pattern(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_row_pattern: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->row_pattern = enable ? 1 : 0;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_row_pattern(const amg_mat *A)
-{
-   return A ? A->rp_n : 0;
-}
-
-extern "C" int amg_set_pair_pattern(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_pair_pattern: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->pair_pattern = enable < 0 ? 0 : enable > 2 ? 2 : enable;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_pair_pattern(const amg_mat *A)
-{
-   return A ? A->pp_n : 0;
-}
-
-extern "C" int amg_set_pair_anchor16(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_pair_anchor16: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->pair_anchor16 = enable ? 1 : 0;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_pair_anchor16(const amg_mat *A)
-{
-   return (A && A->pdelta) ? 1 : 0;
-}
-
-extern "C" int amg_set_master_pattern(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_master_pattern: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->master_pattern = enable ? 1 : 0;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_master_pattern(const amg_mat *A)
-{
-   return A ? A->mp_J * (A->mp_uni ? -1 : 1) : 0;
-}
-
-extern "C" int amg_set_plane_march(amg_ctx *c, int enable, int zc, int xcd)
-{
-   AMG_ARG(c, "amg_set_plane_march: null context");
-   AMG_ARG(zc >= -1 && zc <= 64, "amg_set_plane_march: planes per chunk %d outside [1, 64] (0: keep, -1: auto)",
-           zc);
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->plane_march = enable ? 1 : 0;
-   if (zc > 0) c->mz_zc = zc, c->mz_zc_auto = 0;
-   if (zc == -1) c->mz_zc = 16, c->mz_zc_auto = 1;
-   if (xcd >= 0) c->mz_xcd = xcd ? 1 : 0;
+   *out = A.release();
    return AMG_OK;
 }
 
@@ -1022,228 +390,9 @@ extern "C" int amg_set_fuse_transfer(amg_ctx *c, int enable)
    return AMG_OK;
 }
 
-extern "C" int amg_mat_plane_march(const amg_mat *A)
-{
-   return A ? A->mz_P : 0;
-}
-
-extern "C" int amg_mat_march_points(const amg_mat *A)
-{
-   return (A && A->mz_P) ? (A->mz27 ? 27 : 7) : 0;
-}
-
-extern "C" int amg_set_dict_index(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_dict_index: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->dict_index = enable ? 1 : 0;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_dict_index(const amg_mat *A)
-{
-   return A ? A->dc_n : 0;
-}
-
-extern "C" int amg_set_value_index(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_value_index: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->value_index = enable ? 1 : 0;
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_value_index(const amg_mat *A)
-{
-   return A ? A->vi_n : 0;
-}
-
 int amg_mat_create_device(amg_ctx *c, int nrows, int ncols, long long nnz, amg_mat **out)
 {
    return mat_alloc(c, nrows, ncols, nnz, out);
-}
-
-// 3x3 block form of a square, diagonal-first operator with num_functions = 3
-// (dofs byVDIM: rows 3t..3t+2 are the three components of node t, e.g. the
-// DMEM elasticity problem, DMEM_BuildMatrix.cpp:442-719): block row t is
-// blocked when its three rows hold exactly the columns 3j..3j+2 of the same
-// node set {j} -- each row diagonal first, then ascending, so walking the
-// blocks (ascending j, components ascending) with the diagonal taken first
-// adds every row's products in its CSR order (bit-identical).  Other block
-// rows (the identity rows of fixed dofs) keep the CSR form.  Used only when
-// at least 90% of the block rows are blocked.
-static int build_bsr3(amg_mat *A, const int *rowptr, const int *col, const double *val)
-{
-   const int n = A->nrows, nb = n / 3;
-   if (!A->ctx->bsr3 || n % 3 || n != A->ncols || !A->diag_first || n < 3 || A->nnz < 24LL * n) return AMG_OK;
-   std::vector<int> bptr(nb + 1, 0), bdiag(nb, -1), bcol;
-   std::vector<unsigned char> mode(nb, 1);
-   std::vector<long long> src; // CSR position of every block entry (row-major 3x3), -1 unused
-   std::vector<int> js;
-   long long blocked = 0;
-   for (int t = 0; t < nb; t++) {
-      bptr[t + 1] = bptr[t];
-      const int r0 = 3 * t;
-      const int len = rowptr[r0 + 1] - rowptr[r0];
-      if (len < 3 || len % 3) continue;
-      bool ok = true;
-      js.clear();
-      for (int c = 0; c < 3 && ok; c++) {
-         const int r = r0 + c, b = rowptr[r], e = rowptr[r + 1];
-         ok = e - b == len && col[b] == r;
-         // the row minus its diagonal, ascending, with the diagonal reinserted
-         // at its sorted place: 3j, 3j+1, 3j+2 per node j
-         int prev = -1, k = b + 1;
-         std::vector<int> cols;
-         cols.reserve(len);
-         bool ins = false;
-         for (int q = 0; q < len - 1 && ok; q++, k++) {
-            const int cc = col[k];
-            if (!ins && r < cc) cols.push_back(r), ins = true;
-            ok = cc > prev && cc != r;
-            prev = cc;
-            cols.push_back(cc);
-         }
-         if (!ins) cols.push_back(r);
-         for (int q = 0; q < len && ok; q += 3) {
-            ok = cols[q] % 3 == 0 && cols[q + 1] == cols[q] + 1 && cols[q + 2] == cols[q] + 2;
-            if (ok && c == 0) js.push_back(cols[q] / 3);
-            if (ok && c > 0) ok = js[q / 3] == cols[q] / 3;
-         }
-      }
-      if (!ok) continue;
-      mode[t] = 0;
-      blocked++;
-      for (size_t q = 0; q < js.size(); q++) {
-         if (js[q] == t) bdiag[t] = bptr[t + 1];
-         bcol.push_back(js[q]);
-         bptr[t + 1]++;
-      }
-      if (bdiag[t] < 0) return AMG_OK; // unreachable: every row holds its diagonal
-      // CSR positions: row r's entry for column 3j + cc
-      const size_t base = src.size();
-      src.resize(base + js.size() * 9, -1);
-      for (int c = 0; c < 3; c++) {
-         const int r = r0 + c, b = rowptr[r], e = rowptr[r + 1];
-         for (int k = b; k < e; k++) {
-            const int j = col[k] / 3, cc = col[k] % 3;
-            const size_t q = std::lower_bound(js.begin(), js.end(), j) - js.begin();
-            src[base + q * 9 + 3 * c + cc] = k;
-         }
-      }
-   }
-   if (blocked * 10 < 9LL * nb) return AMG_OK;
-   // sliced layout (21 block rows per slice -- a lane per row -- or, value-indexed
-   // with ctx->bsr3 == 2, 64 -- a lane per block row; padded to the slice's longest)
-   const int SL = A->ctx->bsr3 == 2 && A->vidx ? 64 : 21;
-   A->bsl = SL;
-   const int ns = (nb + SL - 1) / SL;
-   std::vector<long long> soff(ns + 1, 0);
-   for (int sl = 0; sl < ns; sl++) {
-      int w = 0;
-      for (int t = sl * SL; t < std::min(nb, (sl + 1) * SL); t++) w = std::max(w, bptr[t + 1] - bptr[t]);
-      soff[sl + 1] = soff[sl] + (long long)w * SL;
-   }
-   const size_t nslot = (size_t)soff[ns];
-   std::vector<int> scol(std::max<size_t>(nslot, 1), 0), bdk(nb, 0);
-   std::vector<unsigned char> bcnt(nb, 0);
-   for (int t = 0; t < nb; t++) {
-      const int cnt = bptr[t + 1] - bptr[t];
-      if (cnt > 255) return AMG_OK; // block rows of more than 255 blocks: keep CSR
-      bcnt[t] = (unsigned char)cnt;
-      bdk[t] = mode[t] ? 0 : bdiag[t] - bptr[t];
-      const int sl = t / SL, q = t % SL;
-      const int w = (int)((soff[sl + 1] - soff[sl]) / SL);
-      for (int k = 0; k < w; k++) scol[(size_t)soff[sl] + (size_t)k * SL + q] = k < cnt ? bcol[bptr[t] + k] : t;
-   }
-   hipStream_t s = A->ctx->stream;
-   auto fail = [&]() {
-      hipFree(A->soff), hipFree(A->bcol), hipFree(A->bdiag), hipFree(A->bmode), hipFree(A->bvi), hipFree(A->bval);
-      A->soff = nullptr;
-      A->bcol = A->bdiag = nullptr;
-      A->bmode = nullptr;
-      A->bvi = nullptr;
-      A->bval = nullptr;
-      (void)hipGetLastError();
-      return AMG_OK; // not enough room: keep the CSR forms
-   };
-   hipError_t e = hipMalloc(&A->soff, (ns + 1) * sizeof(long long));
-   if (e == hipSuccess) e = hipMalloc(&A->bcol, scol.size() * sizeof(int));
-   if (e == hipSuccess) e = hipMalloc(&A->bdiag, nb * sizeof(int));
-   if (e == hipSuccess) e = hipMalloc(&A->bmode, nb);
-   if (e != hipSuccess) return fail();
-   // slot of block k of block row t
-   auto slot = [&](int t, int k) { return (size_t)soff[t / SL] + (size_t)k * SL + t % SL; };
-   if (A->vidx) {
-      // block entries as indices into the value table (3 rows x 4 bytes)
-      std::vector<double> tab(256);
-      AMG_HIP(hipMemcpy(tab.data(), A->vtab, 256 * sizeof(double), hipMemcpyDeviceToHost));
-      std::vector<unsigned long long> keys(A->vi_n);
-      std::memcpy(keys.data(), tab.data(), A->vi_n * 8);
-      std::vector<unsigned int> bvi(std::max<size_t>(nslot * 3, 1), 0);
-      for (int t = 0; t < nb; t++)
-         for (int k = 0; k < bptr[t + 1] - bptr[t]; k++)
-            for (int q = 0; q < 9; q++) {
-               const long long sp = src[(size_t)(bptr[t] + k) * 9 + q];
-               if (sp < 0) continue;
-               unsigned long long b;
-               std::memcpy(&b, &val[sp], 8);
-               const size_t idx = std::lower_bound(keys.begin(), keys.end(), b) - keys.begin();
-               bvi[slot(t, k) * 3 + q / 3] |= (unsigned int)idx << (8 * (q % 3));
-            }
-      e = hipMalloc(&A->bvi, bvi.size() * 4);
-      if (e != hipSuccess) return fail();
-      AMG_HIP(hipMemcpyAsync(A->bvi, bvi.data(), bvi.size() * 4, hipMemcpyHostToDevice, s));
-      AMG_HIP(hipStreamSynchronize(s));
-      A->bsr3 = 1;
-   } else {
-      std::vector<double> bv(std::max<size_t>(nslot * 9, 1), 0.0);
-      for (int t = 0; t < nb; t++)
-         for (int k = 0; k < bptr[t + 1] - bptr[t]; k++)
-            for (int q = 0; q < 9; q++) {
-               const long long sp = src[(size_t)(bptr[t] + k) * 9 + q];
-               if (sp >= 0) bv[slot(t, k) * 9 + q] = val[sp];
-            }
-      e = hipMalloc(&A->bval, bv.size() * 8);
-      if (e != hipSuccess) return fail();
-      AMG_HIP(hipMemcpyAsync(A->bval, bv.data(), bv.size() * 8, hipMemcpyHostToDevice, s));
-      AMG_HIP(hipStreamSynchronize(s));
-      A->bsr3 = 2;
-   }
-   for (int t = 0; t < nb; t++) bcnt[t] = mode[t] ? 0 : bcnt[t];
-   AMG_HIP(hipMemcpyAsync(A->soff, soff.data(), (ns + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->bcol, scol.data(), scol.size() * sizeof(int), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->bdiag, bdk.data(), nb * sizeof(int), hipMemcpyHostToDevice, s));
-   AMG_HIP(hipMemcpyAsync(A->bmode, bcnt.data(), nb, hipMemcpyHostToDevice, s));
-   AMG_HIP(hipStreamSynchronize(s));
-   return AMG_OK;
-}
-
-extern "C" int amg_set_bsr3(amg_ctx *c, int enable)
-{
-   AMG_ARG(c, "amg_set_bsr3: null context");
-   c->knob_gen++; // cached hipGraphs were captured with the old setting
-   c->bsr3 = enable == 2 ? 2 : (enable ? 1 : 0);
-   return AMG_OK;
-}
-
-extern "C" int amg_mat_bsr3(const amg_mat *A)
-{
-   return A ? A->bsr3 : 0;
-}
-
-extern "C" int amg_mat_bsr3_slice(const amg_mat *A)
-{
-   return A && A->bsr3 ? A->bsl : 0;
-}
-
-extern "C" int amg_mat_bsr3_counts(const amg_mat *A, unsigned char *out)
-{
-   AMG_ARG(A && out, "amg_mat_bsr3_counts: null argument");
-   AMG_ARG(A->bsr3 && A->bmode, "amg_mat_bsr3_counts: the matrix is not in 3x3 block form");
-   AMG_HIP(hipStreamSynchronize(A->ctx->stream));
-   AMG_HIP(hipMemcpy(out, A->bmode, (size_t)(A->nrows / 3), hipMemcpyDeviceToHost));
-   return AMG_OK;
 }
 
 extern "C" int amg_csr_register(amg_ctx *c, int nrows, int ncols, long long nnz, const int *rowptr,
@@ -1255,8 +404,9 @@ extern "C" int amg_csr_register(amg_ctx *c, int nrows, int ncols, long long nnz,
    AMG_ARG(rowptr[nrows] == nnz && rowptr[0] == 0, "amg_csr_register: rowptr[0]=%d rowptr[n]=%d nnz=%lld",
            rowptr[0], rowptr[nrows], nnz);
    AMG_ARG(nrows == 0 || ncols > 0, "amg_csr_register: ncols must be positive");
-   amg_mat *A = nullptr;
-   AMG_TRY(mat_alloc(c, nrows, ncols, nnz, &A));
+   amg_mat *raw = nullptr;
+   AMG_TRY(mat_alloc(c, nrows, ncols, nnz, &raw));
+   amg_mat_ptr A(raw); // freed when a later step fails
    A->diag_first = diag_first;
    AMG_HIP(hipMemcpyAsync(A->rowptr, rowptr, ((size_t)nrows + 1) * sizeof(int),
                           hipMemcpyHostToDevice, c->stream));
@@ -1265,10 +415,10 @@ extern "C" int amg_csr_register(amg_ctx *c, int nrows, int ncols, long long nnz,
       AMG_HIP(hipMemcpyAsync(A->val, val, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice,
                              c->stream));
    }
-   AMG_TRY(amg_mat_finish(A));
+   AMG_TRY(amg_mat_finish(A.get()));
    AMG_HIP(hipStreamSynchronize(c->stream));
-   AMG_TRY(build_bsr3(A, rowptr, col, val));
-   *out = A;
+   AMG_TRY(amg_mat_build_bsr3(A.get(), rowptr, col, val));
+   *out = A.release();
    return AMG_OK;
 }
 
@@ -1281,26 +431,7 @@ extern "C" int amg_mat_free(amg_mat *A)
    hipFree(A->col);
    hipFree(A->val);
    hipFree(A->diag);
-   hipFree(A->vidx);
-   hipFree(A->vtab);
-   hipFree(A->didx);
-   hipFree(A->doff);
-   hipFree(A->dval);
-   hipFree(A->danch);
-   hipFree(A->rpat);
-   hipFree(A->ptab);
-   hipFree(A->ppat);
-   hipFree(A->pptab);
-   hipFree(A->mpmask);
-   hipFree(A->mpval);
-   hipFree(A->soff);
-   hipFree(A->bcol);
-   hipFree(A->bdiag);
-   hipFree(A->bmode);
-   hipFree(A->bvi);
-   hipFree(A->bval);
-   hipFree(A->pbase);
-   hipFree(A->pdelta);
+   amg_mat_drop_forms(A);
    delete A;
    return AMG_OK;
 }

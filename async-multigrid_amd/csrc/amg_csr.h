@@ -1,5 +1,5 @@
 // amg_csr.h -- what the classical setup's files share (amg_classical.cpp,
-// amg_spgemm.hip, amg_trunc.hip, amg_setup_dev.hip; not part of the C-ABI): the
+// amg_spgemm.hip, amg_trunc.hip, amg_setup_dev.hip; DBuf also amg_format.hip; not part of the C-ABI): the
 // host and device CSR types, owning device buffers, the per-call stream, upload /
 // download, the count scan, the row batching, and the entry points the files
 // call across each other.  Device memory is owned: a DBuf or DCsr frees in its
@@ -63,10 +63,27 @@ struct DBuf {
       AMG_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
       return AMG_OK;
    }
+   // the soft form: false when the device has no room, with the HIP error
+   // cleared and no library error set (the caller does without the array)
+   bool try_alloc(size_t count)
+   {
+      release();
+      if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess) return true;
+      p = nullptr;
+      (void)hipGetLastError();
+      return false;
+   }
    void release()
    {
       if (p) hipFree(p);
       p = nullptr;
+   }
+   // the array handed over to the caller, who frees it
+   T *take()
+   {
+      T *q = p;
+      p = nullptr;
+      return q;
    }
    operator T *() const { return p; }
 };

@@ -658,7 +658,8 @@ int build_hier(amg_ctx *c, int L, Partition part, const amg_opts *opts, const Lo
 {
    amg_transport *t = c->xport;
    const int me = t->rank;
-   auto D = std::make_unique<amg_dist_hier>();
+   // a failing step frees what the hierarchy holds so far, its matrices included
+   std::unique_ptr<amg_dist_hier, int (*)(amg_dist_hier *)> D(new amg_dist_hier(), amg_dist_hier_free);
    D->ctx = c;
    D->o = *opts;
    D->L = L;

@@ -10,6 +10,7 @@
 #include <functional>
 #include <string>
 #include <limits>
+#include <memory>
 #include <vector>
 
 #include "amg_mi355x.h"
@@ -253,7 +254,18 @@ struct amg_vec {
 int amg_ctx_partials(amg_ctx *ctx, size_t n, double **out);
 // device CSR allocation (+ diagonal extraction) for in-library builders
 int amg_mat_create_device(amg_ctx *c, int nrows, int ncols, long long nnz, amg_mat **out);
+// a matrix under construction: freed (amg_mat_free) unless released to the caller
+struct amg_mat_deleter {
+   void operator()(amg_mat *A) const { amg_mat_free(A); }
+};
+using amg_mat_ptr = std::unique_ptr<amg_mat, amg_mat_deleter>;
+// the compressed forms (amg_format.hip): the diagonal and the ladder of forms of
+// a matrix whose CSR arrays are on the device (or on their way there on the
+// context's stream); the 3x3 block form from the host CSR of a finished matrix,
+// the stream synchronised; every form's arrays freed (amg_mat_free)
 int amg_mat_finish(amg_mat *A);
+int amg_mat_build_bsr3(amg_mat *A, const int *rowptr, const int *col, const double *val);
+void amg_mat_drop_forms(amg_mat *A);
 // coarse sub-cycle of a hierarchy whose level 0 is an inner level of a larger
 // one: f_dev -> level-0 correction (zero start, SMEM_Sync_Parfor_Vcycle from
 // that level down); returns the level-0 iterate pointer in *u_dev
@@ -435,31 +447,6 @@ void atomic_add(hipStream_t s, double *u, const double *x, int rb, int re);
 void stream_triad(hipStream_t s, double *a, const double *b, const double *c, double q, long long n);
 // PMC calibration streams: mode 0/1/2/3 = read bytes with 16/8/4/1-byte lanes, 4 = 8-byte writes
 void calib_stream(hipStream_t s, int mode, void *buf, long long bytes, double *out);
-
-// value-indexed CSR construction
-void vi_collect(hipStream_t s, const double *val, long long nnz, unsigned long long *slots, int nslots,
-                int *count);
-void vi_encode(hipStream_t s, const double *val, long long nnz, const unsigned long long *keys, int T,
-               unsigned char *vidx);
-
-// row-pattern construction (needs the dictionary index)
-void rp_collect(hipStream_t s, const amg_mat *A, unsigned long long *slots, int *rep, int nslots, int *count,
-                int *bad);
-void rp_table(hipStream_t s, const amg_mat *A, const int *rep, int T, unsigned char *ptab);
-void rp_encode(hipStream_t s, const amg_mat *A, const unsigned long long *keys, int T,
-               const unsigned char *ptab, unsigned char *rpat, int *bad);
-void pp_collect(hipStream_t s, const amg_mat *A, unsigned char *flags);
-// slab-compressed anchors (pbase, pdelta); ok set to 0 when a slab's range
-// exceeds 16 bits
-void pp_anchor_compress(hipStream_t s, const amg_mat *A, int *pbase, unsigned short *pdelta, int *ok);
-void pp_encode(hipStream_t s, const amg_mat *A, const unsigned char *map, unsigned char *ppat,
-               unsigned long long *counts);
-
-// dictionary-coded CSR construction (needs the value index)
-void dc_collect(hipStream_t s, const amg_mat *A, unsigned long long *slots, int nslots, int *count,
-                int *maxlen);
-void dc_encode(hipStream_t s, const amg_mat *A, const unsigned long long *keys, int T,
-               unsigned char *didx, int *anch);
 
 // deterministic reductions: red_blocks(n) workgroups of 256 lanes, lane t of
 // workgroup b adding i = 256 b + t, += 256 gridDim, then block_sum_256's tree

@@ -6556,395 +6556,4 @@ void reduce_partials(hipStream_t s, const double *partials, int np, double *out,
    if (do_sqrt) finish_k<<<1, 1, 0, s>>>(out, do_sqrt);
 }
 
-// ---------------------------------------------------------------------------
-// value-indexed CSR construction: the distinct values of val (by bit pattern)
-// collected into a device hash set, then every entry encoded as a one-byte
-// index into the sorted table of at most 256 values
-// ---------------------------------------------------------------------------
-constexpr unsigned long long VI_EMPTY = ~0ULL;
-
-__device__ __forceinline__ unsigned int vi_hash(unsigned long long k)
-{
-   k ^= k >> 33;
-   k *= 0xff51afd7ed558ccdULL;
-   k ^= k >> 33;
-   return (unsigned int)k;
-}
-
-__device__ __forceinline__ void vi_insert(unsigned long long key, unsigned long long *slots,
-                                          int nslots, int *count)
-{
-   if (__atomic_load_n(count, __ATOMIC_RELAXED) > 256) return; // table already useless
-   unsigned int h = vi_hash(key) & (nslots - 1);
-   for (int probe = 0; probe < nslots; probe++) {
-      const unsigned long long cur = __atomic_load_n(&slots[h], __ATOMIC_RELAXED);
-      if (cur == key) return;
-      if (cur == VI_EMPTY) {
-         const unsigned long long prev = atomicCAS(&slots[h], VI_EMPTY, key);
-         if (prev == VI_EMPTY) {
-            atomicAdd(count, 1);
-            return;
-         }
-         if (prev == key) return;
-      }
-      h = (h + 1) & (nslots - 1);
-   }
-}
-
-// CSR-DC keys: (col - row) in the high 32 bits, the value-index byte low
-__device__ __forceinline__ unsigned long long dc_key(int off, unsigned char b)
-{
-   return ((unsigned long long)(unsigned int)off << 8) | b;
-}
-
-// anchor of row i: its first column (the diagonal for diag-first square
-// operators, the parent coarse point for interpolation rows)
-__global__ void dc_collect_k(const int *__restrict__ rowptr, const int *__restrict__ col,
-                             const unsigned char *__restrict__ vidx, int n,
-                             unsigned long long *slots, int nslots, int *count, int *maxlen)
-{
-   unsigned long long last0 = VI_EMPTY, last1 = VI_EMPTY;
-   int ml = 0, offrow = 0;
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-      const int rs = rowptr[i], re = rowptr[i + 1];
-      ml = max(ml, re - rs);
-      const int anc = rs < re ? col[rs] : i;
-      offrow |= (anc != i);
-      for (int k = rs; k < re; k++) {
-         const unsigned long long key = dc_key(col[k] - anc, vidx[k]);
-         if (key == last0 || key == last1) continue;
-         last1 = last0;
-         last0 = key;
-         vi_insert(key, slots, nslots, count);
-      }
-   }
-   atomicMax(maxlen, ml);
-   if (offrow) atomicOr(maxlen + 1, 1); // some row's anchor is not its own index
-}
-
-__global__ void dc_encode_k(const int *__restrict__ rowptr, const int *__restrict__ col,
-                            const unsigned char *__restrict__ vidx, int n,
-                            const unsigned long long *__restrict__ keys, int T,
-                            unsigned char *__restrict__ didx, int *__restrict__ anch)
-{
-   __shared__ unsigned long long tk[256];
-   if (threadIdx.x < 256) tk[threadIdx.x] = threadIdx.x < T ? keys[threadIdx.x] : VI_EMPTY;
-   __syncthreads();
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-      const int rs = rowptr[i], re = rowptr[i + 1];
-      const int anc = rs < re ? col[rs] : i;
-      if (anch) anch[i] = anc;
-      for (int k = rs; k < re; k++) {
-         const unsigned long long key = dc_key(col[k] - anc, vidx[k]);
-         int lo = 0, hi = T - 1;
-         while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (tk[mid] < key)
-               lo = mid + 1;
-            else
-               hi = mid;
-         }
-         didx[k] = (unsigned char)lo;
-      }
-   }
-}
-
-// ---- row-pattern construction ------------------------------------------------
-// key of row i's dictionary sequence: exact for <= 7 entries (length byte +
-// the entries), else a 56-bit hash above the length byte (verified after
-// encoding, so a collision only disables the format)
-__device__ __forceinline__ unsigned long long rp_key(const unsigned char *__restrict__ didx, int rs, int len)
-{
-   if (len <= 7) {
-      unsigned long long k = (unsigned long long)len;
-      for (int j = 0; j < len; j++) k |= (unsigned long long)didx[rs + j] << (8 * (j + 1));
-      return k;
-   }
-   unsigned long long h = 0xcbf29ce484222325ULL ^ (unsigned long long)len;
-   for (int j = 0; j < len; j++) h = (h ^ didx[rs + j]) * 0x100000001b3ULL;
-   h ^= h >> 29;
-   h *= 0xbf58476d1ce4e5b9ULL;
-   h ^= h >> 32;
-   return (h << 8) | (unsigned long long)len;
-}
-
-// distinct row keys into slots (first row of each into rep), and the number of
-// rows that cannot be coded (empty or longer than AMG_DC_MAXROW)
-__global__ void rp_collect_k(const int *__restrict__ rowptr, const unsigned char *__restrict__ didx, int n,
-                             unsigned long long *slots, int *rep, int nslots, int *count, int *bad)
-{
-   unsigned long long last = VI_EMPTY;
-   int nbad = 0;
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-      const int rs = rowptr[i], len = rowptr[i + 1] - rs;
-      if (len < 1 || len > AMG_DC_MAXROW) {
-         nbad++;
-         continue;
-      }
-      const unsigned long long key = rp_key(didx, rs, len);
-      if (key == last) continue;
-      last = key;
-      if (__atomic_load_n(count, __ATOMIC_RELAXED) > 256) continue; // too many patterns: only count bad rows
-      unsigned int h = vi_hash(key) & (nslots - 1);
-      for (int probe = 0; probe < nslots; probe++) {
-         const unsigned long long cur = __atomic_load_n(&slots[h], __ATOMIC_RELAXED);
-         if (cur == key) break;
-         if (cur == VI_EMPTY) {
-            const unsigned long long prev = atomicCAS(&slots[h], VI_EMPTY, key);
-            if (prev == VI_EMPTY) {
-               atomicAdd(count, 1);
-               rep[h] = i;
-               break;
-            }
-            if (prev == key) break;
-         }
-         h = (h + 1) & (nslots - 1);
-      }
-   }
-   if (nbad) atomicAdd(bad, nbad);
-}
-
-// pattern table: entry t = [length, dictionary bytes of representative row rep[t]]
-__global__ void rp_table_k(const int *__restrict__ rowptr, const unsigned char *__restrict__ didx,
-                           const int *__restrict__ rep, int T, unsigned char *__restrict__ ptab)
-{
-   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-   if (t >= T) return;
-   const int rs = rowptr[rep[t]], len = rowptr[rep[t] + 1] - rs;
-   unsigned char *pp = ptab + t * AMG_RP_STRIDE;
-   pp[0] = (unsigned char)len;
-   for (int j = 0; j < AMG_DC_MAXROW; j++) pp[1 + j] = j < len ? didx[rs + j] : 0;
-}
-
-// rpat[i] = index of row i's key among the T sorted keys; rows whose bytes
-// differ from their pattern (a hash collision) are counted in bad
-__global__ void rp_encode_k(const int *__restrict__ rowptr, const unsigned char *__restrict__ didx, int n,
-                            const unsigned long long *__restrict__ keys, int T,
-                            const unsigned char *__restrict__ ptab, unsigned char *__restrict__ rpat,
-                            int *bad)
-{
-   __shared__ unsigned long long tk[256];
-   if (threadIdx.x < 256) tk[threadIdx.x] = threadIdx.x < T ? keys[threadIdx.x] : VI_EMPTY;
-   __syncthreads();
-   int nbad = 0;
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-      const int rs = rowptr[i], len = rowptr[i + 1] - rs;
-      const unsigned long long key = rp_key(didx, rs, len);
-      int lo = 0, hi = T - 1;
-      while (lo < hi) {
-         const int mid = (lo + hi) >> 1;
-         if (tk[mid] < key)
-            lo = mid + 1;
-         else
-            hi = mid;
-      }
-      rpat[i] = (unsigned char)lo;
-      const unsigned char *pp = ptab + lo * AMG_RP_STRIDE;
-      bool ok = tk[lo] == key && pp[0] == len;
-      for (int j = 0; ok && j < len; j++) ok = pp[1 + j] == didx[rs + j];
-      nbad += !ok;
-   }
-   if (nbad) atomicAdd(bad, nbad);
-}
-
-// row-pair keys p0 * 257 + p1 (p1 = 256 when row 2t+1 does not exist)
-// pair key: (pattern of row 2t, of row 2t+1 or 256 if none, anchor delta
-// da = anch[2t+1] - anch[2t] + AMG_PP_DA0 in [0, AMG_PP_NDA)); a delta out of
-// range flags the matrix (flags[AMG_PP_NK])
-__device__ __forceinline__ int pp_key(const unsigned char *__restrict__ rpat, const int *__restrict__ anch, int n,
-                                      int t)
-{
-   const bool two = 2 * t + 1 < n;
-   const int da = (two && anch) ? anch[2 * t + 1] - anch[2 * t] + AMG_PP_DA0 : AMG_PP_DA0;
-   if (da < 0 || da >= AMG_PP_NDA) return -1;
-   return (rpat[2 * t] * 257 + (two ? rpat[2 * t + 1] : 256)) * AMG_PP_NDA + da;
-}
-
-__global__ void pp_collect_k(const unsigned char *__restrict__ rpat, const int *__restrict__ anch, int n,
-                             unsigned char *flags)
-{
-   const int np = (n + 1) / 2;
-   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < np; t += gridDim.x * blockDim.x) {
-      int k = pp_key(rpat, anch, n, t);
-      if (k < 0) k = AMG_PP_NK;
-      if (!flags[k]) flags[k] = 1;
-   }
-}
-
-// ppat[t] = the pair's table index; counts[p] += pairs of pattern p
-__global__ __launch_bounds__(256) void pp_encode_k(const unsigned char *__restrict__ rpat,
-                                                   const int *__restrict__ anch, int n,
-                                                   const unsigned char *__restrict__ map,
-                                                   unsigned char *__restrict__ ppat,
-                                                   unsigned long long *__restrict__ counts)
-{
-   __shared__ unsigned int hist[256];
-   hist[threadIdx.x] = 0;
-   __syncthreads();
-   const int np = (n + 1) / 2;
-   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < np; t += gridDim.x * blockDim.x) {
-      const unsigned char p = map[pp_key(rpat, anch, n, t)];
-      ppat[t] = p;
-      atomicAdd(&hist[p], 1u);
-   }
-   __syncthreads();
-   if (hist[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-}
-
-void pp_collect(hipStream_t s, const amg_mat *A, unsigned char *flags)
-{
-   if (A->nrows <= 0) return;
-   pp_collect_k<<<std::min(8192, (A->nrows + 511) / 512), 256, 0, s>>>(A->rpat, A->danch, A->nrows, flags);
-}
-
-// one workgroup per 512-row slab: least anchor of its even rows, then each
-// pair's 16-bit delta from it
-__global__ __launch_bounds__(256) void pp_anchor_k(const int *__restrict__ anch, int n, int *__restrict__ pbase,
-                                                  unsigned short *__restrict__ pdelta, int *__restrict__ ok)
-{
-   __shared__ int red[2][256];
-   const int slab = (int)blockIdx.x, tid = (int)threadIdx.x;
-   const long long row = (long long)slab * 512 + 2 * tid;
-   const int a = row < n ? anch[row] : INT_MAX;
-   red[0][tid] = a;
-   red[1][tid] = row < n ? a : INT_MIN;
-   __syncthreads();
-   for (int w = 128; w > 0; w >>= 1) {
-      if (tid < w) {
-         red[0][tid] = min(red[0][tid], red[0][tid + w]);
-         red[1][tid] = max(red[1][tid], red[1][tid + w]);
-      }
-      __syncthreads();
-   }
-   const int lo = red[0][0], hi = red[1][0];
-   if (tid == 0) {
-      pbase[slab] = lo;
-      if ((long long)hi - lo > 65535) *ok = 0;
-   }
-   if (row < n) pdelta[row >> 1] = (unsigned short)(a - lo);
-}
-
-void pp_anchor_compress(hipStream_t s, const amg_mat *A, int *pbase, unsigned short *pdelta, int *ok)
-{
-   const int ns = (A->nrows + 511) / 512;
-   if (ns > 0) pp_anchor_k<<<ns, 256, 0, s>>>(A->danch, A->nrows, pbase, pdelta, ok);
-}
-
-void pp_encode(hipStream_t s, const amg_mat *A, const unsigned char *map, unsigned char *ppat,
-               unsigned long long *counts)
-{
-   if (A->nrows <= 0) return;
-   pp_encode_k<<<std::min(8192, (A->nrows + 511) / 512), 256, 0, s>>>(A->rpat, A->danch, A->nrows, map, ppat,
-                                                                        counts);
-}
-
-void rp_collect(hipStream_t s, const amg_mat *A, unsigned long long *slots, int *rep, int nslots, int *count,
-                int *bad)
-{
-   if (A->nrows <= 0) return;
-   rp_collect_k<<<std::min(8192, (A->nrows + 255) / 256), 256, 0, s>>>(A->rowptr, A->didx, A->nrows, slots,
-                                                                         rep, nslots, count, bad);
-}
-
-void rp_table(hipStream_t s, const amg_mat *A, const int *rep, int T, unsigned char *ptab)
-{
-   if (T > 0) rp_table_k<<<1, 256, 0, s>>>(A->rowptr, A->didx, rep, T, ptab);
-}
-
-void rp_encode(hipStream_t s, const amg_mat *A, const unsigned long long *keys, int T,
-               const unsigned char *ptab, unsigned char *rpat, int *bad)
-{
-   if (A->nrows <= 0) return;
-   rp_encode_k<<<std::min(8192, (A->nrows + 255) / 256), 256, 0, s>>>(A->rowptr, A->didx, A->nrows, keys, T,
-                                                                        ptab, rpat, bad);
-}
-
-void dc_collect(hipStream_t s, const amg_mat *A, unsigned long long *slots, int nslots, int *count,
-                int *maxlen)
-{
-   if (A->nrows <= 0) return;
-   dc_collect_k<<<std::min(8192, (A->nrows + 255) / 256), 256, 0, s>>>(
-      A->rowptr, A->col, A->vidx, A->nrows, slots, nslots, count, maxlen);
-}
-
-void dc_encode(hipStream_t s, const amg_mat *A, const unsigned long long *keys, int T,
-               unsigned char *didx, int *anch)
-{
-   if (A->nrows <= 0) return;
-   dc_encode_k<<<std::min(8192, (A->nrows + 255) / 256), 256, 0, s>>>(A->rowptr, A->col, A->vidx,
-                                                                        A->nrows, keys, T, didx, anch);
-}
-
-__global__ void vi_collect_k(const double *__restrict__ val, long long nnz,
-                             unsigned long long *slots, int nslots, int *count)
-{
-   unsigned long long last0 = VI_EMPTY, last1 = VI_EMPTY;
-   const long long stride = (long long)gridDim.x * blockDim.x;
-   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nnz; i += stride) {
-      const unsigned long long key = (unsigned long long)__double_as_longlong(val[i]);
-      if (key == last0 || key == last1) continue;
-      last1 = last0;
-      last0 = key;
-      if (key == VI_EMPTY) {
-         atomicAdd(count, 1 << 20); // the sentinel pattern itself: give up on the table
-         continue;
-      }
-      // more than 256 distinct values: the table is useless, stop probing
-      // (a nearly full table would cost nslots probes per new value)
-      if (__atomic_load_n(count, __ATOMIC_RELAXED) > 256) return;
-      unsigned int h = vi_hash(key) & (nslots - 1);
-      for (int probe = 0; probe < nslots; probe++) {
-         const unsigned long long cur = __atomic_load_n(&slots[h], __ATOMIC_RELAXED);
-         if (cur == key) break;
-         if (cur == VI_EMPTY) {
-            const unsigned long long prev = atomicCAS(&slots[h], VI_EMPTY, key);
-            if (prev == VI_EMPTY) {
-               atomicAdd(count, 1);
-               break;
-            }
-            if (prev == key) break;
-         }
-         h = (h + 1) & (nslots - 1);
-      }
-   }
-}
-
-__global__ void vi_encode_k(const double *__restrict__ val, long long nnz,
-                            const unsigned long long *__restrict__ keys, int T,
-                            unsigned char *__restrict__ vidx)
-{
-   __shared__ unsigned long long tk[256];
-   if (threadIdx.x < 256) tk[threadIdx.x] = threadIdx.x < T ? keys[threadIdx.x] : VI_EMPTY;
-   __syncthreads();
-   const long long stride = (long long)gridDim.x * blockDim.x;
-   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nnz; i += stride) {
-      const unsigned long long key = (unsigned long long)__double_as_longlong(val[i]);
-      int lo = 0, hi = T - 1;
-      while (lo < hi) {
-         const int mid = (lo + hi) >> 1;
-         if (tk[mid] < key)
-            lo = mid + 1;
-         else
-            hi = mid;
-      }
-      vidx[i] = (unsigned char)lo;
-   }
-}
-
-void vi_collect(hipStream_t s, const double *val, long long nnz, unsigned long long *slots, int nslots,
-                int *count)
-{
-   if (nnz <= 0) return;
-   const long long nb = std::min<long long>(8192, (nnz + 255) / 256);
-   vi_collect_k<<<(int)nb, 256, 0, s>>>(val, nnz, slots, nslots, count);
-}
-
-void vi_encode(hipStream_t s, const double *val, long long nnz, const unsigned long long *keys, int T,
-               unsigned char *vidx)
-{
-   if (nnz <= 0) return;
-   const long long nb = std::min<long long>(8192, (nnz + 255) / 256);
-   vi_encode_k<<<(int)nb, 256, 0, s>>>(val, nnz, keys, T, vidx);
-}
-
 } // namespace amgk

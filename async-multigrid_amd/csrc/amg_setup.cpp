@@ -367,8 +367,6 @@ extern "C" int amg_rhs_rand(long long r0, long long r1, double lo, double hi, do
 
 // device-side generation: rows computed on the host in plane batches and
 // streamed into the device CSR (keeps host memory bounded for 512^3).
-int amg_mat_create_device(amg_ctx *c, int nrows, int ncols, long long nnz, amg_mat **out);
-int amg_mat_finish(amg_mat *A);
 
 // Rows of planes [e0, e1) of the operator's row grid (rows of planes outside
 // [o0, o1) are "ghost" rows: A keeps its whole row when every column lies in
@@ -424,8 +422,9 @@ int amg_gen_register_ext(amg_ctx *ctx, const amg_gen *g, int which, int level, i
    const long long nnz = amg_gen_nnz(g, which, level, o0, o1) + ghost_nnz;
    AMG_ARG(nnz >= 0 && nnz < (1LL << 31) - AMG_NNZ_PAD, "amg_gen_register: nnz %lld", nnz);
    AMG_ARG(nrows < (1LL << 31) && ncols < (1LL << 31), "amg_gen_register: %lld x %lld exceeds int32", nrows, ncols);
-   amg_mat *A = nullptr;
-   AMG_TRY(amg_mat_create_device(ctx, (int)nrows, (int)std::max(1LL, ncols), nnz, &A));
+   amg_mat *raw = nullptr;
+   AMG_TRY(amg_mat_create_device(ctx, (int)nrows, (int)std::max(1LL, ncols), nnz, &raw));
+   amg_mat_ptr A(raw); // freed when a later step fails
    // batches of planes, double-buffered through pinned host memory
    const int np = e1 - e0;
    // ~16M entries (~190 MB of pinned staging) per batch
@@ -488,14 +487,14 @@ int amg_gen_register_ext(amg_ctx *ctx, const amg_gen *g, int which, int level, i
    rp_all[0] = 0;
    AMG_HIP(hipMemcpyAsync(A->rowptr, rp_all.data(), (nrows + 1) * sizeof(int), hipMemcpyHostToDevice,
                           ctx->stream));
-   AMG_TRY(amg_mat_finish(A));
+   AMG_TRY(amg_mat_finish(A.get()));
    AMG_HIP(hipStreamSynchronize(ctx->stream));
    for (int b = 0; b < 2; b++) {
       hipHostFree(hcol[b]);
       hipHostFree(hval[b]);
       hipEventDestroy(done[b]);
    }
-   *out = A;
+   *out = A.release();
    return AMG_OK;
 }
 

@@ -1,5 +1,5 @@
 """Crafted num_functions = 3 operators for the 3x3 block kernels, and a
-restatement of build_bsr3's selection rule (csrc/amg_api.cpp).
+restatement of the selection rule of amg_mat_build_bsr3 (csrc/amg_format.hip).
 
 Pure numpy, seeded, no GPU: tests/test_bsr_cases.py pins what the generator
 contains, tests/test_gpu_bsr_edges.py runs the kernels on it.

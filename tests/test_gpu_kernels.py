@@ -8,6 +8,7 @@ restatement of the reference loops.
 import numpy as np
 import pytest
 
+import format_ref
 from conftest import random_csr, rng
 
 pytestmark = pytest.mark.gpu
@@ -116,7 +117,7 @@ def test_value_index_selection(mats):
     which stay plain CSR (0): decided by the number of distinct values."""
     host, dev = mats
     for name in ALL:
-        nd = np.unique(host[name].val.view(np.int64)).size
+        nd = format_ref.value_count(host[name])
         want = nd if nd <= 256 else 0
         assert dev[name].value_index == want, (name, nd, dev[name].value_index)
     assert dev["lap16"].value_index == 2
@@ -131,13 +132,9 @@ def test_value_index_selection(mats):
     # (a row = its sequence of (column - first column, value) pairs)
     for name in ALL:
         A = host[name]
-        pats = set()
-        for i in range(A.nrows):
-            c = A.col[A.rowptr[i]:A.rowptr[i + 1]].astype(np.int64)
-            v = A.val[A.rowptr[i]:A.rowptr[i + 1]].view(np.int64)
-            pats.add(tuple((c - c[0]).tolist()) + tuple(v.tolist()) if c.size else ())
-        ok = dev[name].dict_index > 0 and np.all(np.diff(A.rowptr) > 0) and len(pats) <= 256
-        assert dev[name].row_pattern == (len(pats) if ok else 0), (name, len(pats), dev[name].row_pattern)
+        npat = format_ref.row_patterns(A)
+        ok = dev[name].dict_index > 0 and np.all(np.diff(A.rowptr) > 0) and npat <= 256
+        assert dev[name].row_pattern == (npat if ok else 0), (name, npat, dev[name].row_pattern)
     assert dev["lap16"].row_pattern == 27  # interior, 6 faces, 12 edges, 8 corners
     assert dev["lap_hole"].dict_index == 7 and dev["lap_hole"].row_pattern == 0
     for name in ("A1", "P0", "R0"):
@@ -151,49 +148,8 @@ def test_value_index_selection(mats):
         if not dev[name].row_pattern or A.nrows == 0:
             assert dev[name].pair_pattern == 0, name
             continue
-        lens = np.diff(A.rowptr)
-        anch = A.col[A.rowptr[:-1]].astype(np.int64)
-        # every row starts at its own index: no anchor array (square, or a slab)
-        anch_is_row = bool(np.all(anch == np.arange(A.nrows)))
-        pat = []
-        for i in range(A.nrows):
-            c = A.col[A.rowptr[i]:A.rowptr[i + 1]].astype(np.int64)
-            v = A.val[A.rowptr[i]:A.rowptr[i + 1]].view(np.int64)
-            pat.append(tuple((c - c[0]).tolist()) + tuple(v.tolist()))
-        pairs, da_ok = set(), True
-        # a row's entries as (column relative to its anchor) for the merge test
-        rel = [tuple((A.col[A.rowptr[i]:A.rowptr[i + 1]].astype(np.int64) - anch[i]).tolist())
-               for i in range(A.nrows)]
-        for t in range((A.nrows + 1) // 2):
-            if 2 * t + 1 < A.nrows:
-                da = int(anch[2 * t + 1] - anch[2 * t])
-                da_ok &= -8 <= da < 8
-                pairs.add((pat[2 * t], pat[2 * t + 1], da))
-            else:
-                pairs.add((pat[2 * t], None, 0))
-        stride = 17 if lens.max() <= 8 else 65
-        # merged list = shortest common supersequence: la + lb - LCS, entries
-        # matched when row 2t+1's column is row 2t's + 1 (anchor delta da)
-        merged = single = 0
-        seen = {}
-        for t in range(A.nrows // 2):
-            key = (pat[2 * t], pat[2 * t + 1], int(anch[2 * t + 1] - anch[2 * t]))
-            if key in seen:  # counted over all row pairs
-                merged += seen[key][0]
-                single += seen[key][1]
-                continue
-            ra, rb_ = rel[2 * t], rel[2 * t + 1]
-            da = key[2] if not anch_is_row else 1
-            L = np.zeros((len(ra) + 1, len(rb_) + 1), dtype=np.int64)
-            for i in range(len(ra) - 1, -1, -1):
-                for j in range(len(rb_) - 1, -1, -1):
-                    L[i, j] = L[i + 1, j + 1] + 1 if rb_[j] + da == ra[i] + 1 else max(L[i + 1, j], L[i, j + 1])
-            seen[key] = (len(ra) + len(rb_) - L[0, 0], max(len(ra), len(rb_)))
-            merged += seen[key][0]
-            single += seen[key][1]
-        ok = (da_ok and lens.max() <= 32 and len(pairs) <= 256 and len(pairs) * stride * 4 <= 32768
-              and merged <= 1.15 * single)
-        assert dev[name].pair_pattern == (len(pairs) if ok else 0), (name, len(pairs), dev[name].pair_pattern)
+        npair, ok = format_ref.pair_patterns(A)
+        assert dev[name].pair_pattern == (npair if ok else 0), (name, npair, dev[name].pair_pattern)
     # 16^3 (x even): pairs (x=0,1), (2k,2k+1) interior, (14,15) times 9 (y,z) classes
     assert dev["lap16"].pair_pattern == 27
     assert dev["A1"].pair_pattern > 0  # the 27-pt Galerkin operator
