@@ -259,6 +259,15 @@ class Context:
         v.upload(a)
         return v
 
+    def mvec(self, array_or_shape):
+        """A device multivector: from an n x k array (uploaded) or a shape (n, k) (zero); k is 2, 4 or 8."""
+        if isinstance(array_or_shape, tuple):
+            n, k = array_or_shape
+            return Mvec(self, int(n), int(k))
+        a = np.ascontiguousarray(array_or_shape, dtype=np.float64)
+        assert a.ndim == 2
+        return Mvec(self, a.shape[0], a.shape[1]).upload(a)
+
     def close(self):
         if self.h:
             lib.amg_finalize(self.h)
@@ -347,6 +356,87 @@ class Vec:
         if self.h and self._owns:
             lib.amg_vec_free(self.h)
         self.h = None
+
+
+MRHS_WIDTHS = (2, 4, 8)
+
+
+def pack_columns(vectors):
+    """The n x k row-major array of 1 to 8 vectors of one length, padded with zero columns to
+    the next multivector width (2, 4 or 8)."""
+    cols = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in vectors]
+    if not 1 <= len(cols) <= MRHS_WIDTHS[-1]:
+        raise ValueError(f"pack_columns: {len(cols)} vectors (1 to {MRHS_WIDTHS[-1]})")
+    n = cols[0].size
+    if any(c.size != n for c in cols):
+        raise ValueError("pack_columns: the vectors differ in length")
+    k = next(w for w in MRHS_WIDTHS if w >= len(cols))
+    out = np.zeros((n, k))
+    for j, c in enumerate(cols):
+        out[:, j] = c
+    return out
+
+
+def unpack_columns(array, count):
+    """The first count columns of an n x k array as contiguous vectors."""
+    a = np.asarray(array)
+    if a.ndim != 2 or not 0 <= count <= a.shape[1]:
+        raise ValueError(f"unpack_columns: {count} columns of an array of shape {a.shape}")
+    return [np.ascontiguousarray(a[:, j]) for j in range(count)]
+
+
+class Mvec:
+    """Device multivector, n x k fp64 row-major, k in {2, 4, 8} (amg_mvec_create)."""
+
+    def __init__(self, ctx, n, k):
+        h = C.c_void_p()
+        check(lib.amg_mvec_create(ctx.h, int(n), int(k), C.byref(h)))
+        self.ctx, self.n, self.k, self.h = ctx, int(n), int(k), h
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.shape == (self.n, self.k), (a.shape, self.n, self.k)
+        check(lib.amg_mvec_upload(self.ctx.h, self.h, _dp(a)))
+        return self
+
+    def download(self):
+        out = np.empty((self.n, self.k), dtype=np.float64)
+        check(lib.amg_mvec_download(self.ctx.h, self.h, _dp(out)))
+        return out
+
+    def col(self, j, out=None):
+        """Column j as a Vec (unpacked on the device; out given or created)."""
+        v = Vec(self.ctx, self.n) if out is None else out
+        check(lib.amg_mvec_get_col(self.ctx.h, self.h, int(j), v.h))
+        return v
+
+    def set_col(self, j, x):
+        """Column j = the Vec x (packed on the device)."""
+        check(lib.amg_mvec_set_col(self.ctx.h, self.h, int(j), x.h))
+
+    def set(self, a):
+        check(lib.amg_mvec_set(self.ctx.h, self.h, float(a)))
+
+    def axpy(self, alpha, x):
+        """self(:, j) += alpha[j] x(:, j)"""
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        assert a.size == self.k
+        check(lib.amg_mvec_axpy(self.ctx.h, _dp(a), x.h, self.h))
+
+    def dot(self, y):
+        out = np.zeros(self.k)
+        check(lib.amg_mvec_dot(self.ctx.h, self.h, y.h, _dp(out)))
+        return out
+
+    def norm2(self):
+        out = np.zeros(self.k)
+        check(lib.amg_mvec_norm2(self.ctx.h, self.h, _dp(out)))
+        return out
+
+    def free(self):
+        if self.h:
+            lib.amg_mvec_free(self.h)
+            self.h = None
 
 
 class Hier:
@@ -514,6 +604,65 @@ class Hier:
         emax, emin, k = C.c_double(), C.c_double(), C.c_int()
         check(lib.amg_pcg_eigs(self.h, C.byref(emax), C.byref(emin), C.byref(k)))
         return emax.value, emin.value, k.value
+
+    def _mrhs_in(self, vectors, default=None):
+        """(Mvec, count, owned): a list of 1 to 8 host vectors packed and uploaded, or an Mvec as it is"""
+        if isinstance(vectors, Mvec):
+            return vectors, vectors.k, False
+        if vectors is None:
+            return self.ctx.mvec((self.n0, default)), default, True
+        m = self.ctx.mvec(pack_columns(vectors))
+        return m, len(vectors), True
+
+    def mrhs_precond_apply(self, r, z=None):
+        """z(:, j) = M^-1 r(:, j) for every column at once (amg_mrhs_precond_apply).  Mvec in, Mvec
+        out (z given or created, no host sync); a list of 1 to 8 vectors in, a list of arrays out."""
+        rv, count, owned = self._mrhs_in(r)
+        zv = Mvec(self.ctx, self.n0, rv.k) if z is None else z
+        check(lib.amg_mrhs_precond_apply(self.h, rv.h, zv.h))
+        if not owned:
+            return zv
+        out = unpack_columns(zv.download(), count)
+        rv.free()
+        zv.free()
+        return out
+
+    def _mrhs_run(self, fn, f, x0):
+        fv, count, owned = self._mrhs_in(f)
+        if isinstance(x0, Mvec):
+            xv, xowned = x0, False
+        else:
+            xv, _, xowned = self._mrhs_in(x0, default=fv.k)
+        hist = np.zeros((self.opts.num_cycles + 1, fv.k))
+        k = C.c_int()
+        check(fn(self.h, fv.h, xv.h, _dp(hist), C.byref(k)))
+        hist = hist[:k.value + 1, :count]
+        if not xowned:
+            out = xv
+        else:
+            out = unpack_columns(xv.download(), count)
+            xv.free()
+        if owned:
+            fv.free()
+        return out, hist, k.value
+
+    def mrhs_solve(self, f, u0=None):
+        """SMEM_Solve on 1 to 8 right-hand sides at once (amg_mrhs_solve): a list of vectors (or an
+        Mvec) in; returns (iterates, residual-norm history of shape (cycles + 1, count), cycles).
+        u0: a list as long as f, an Mvec (overwritten with the iterates and returned), or None."""
+        return self._mrhs_run(lib.amg_mrhs_solve, f, u0)
+
+    def mrhs_pcg_solve(self, f, x0=None):
+        """AMG-preconditioned CG on 1 to 8 right-hand sides in lockstep (amg_mrhs_pcg_solve);
+        arguments and returns as mrhs_solve."""
+        return self._mrhs_run(lib.amg_mrhs_pcg_solve, f, x0)
+
+    def mrhs_pcg_scalars(self, col, cap=4096):
+        """(alpha, beta, rho) of column col of the last mrhs_pcg_solve, oldest first."""
+        a, b, r = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        n = C.c_int()
+        check(lib.amg_mrhs_pcg_scalars(self.h, int(col), _dp(a), _dp(b), _dp(r), int(cap), C.byref(n)))
+        return a[:n.value], b[:n.value], r[:n.value]
 
     def profile(self, reset=True):
         ms = np.zeros(5)

@@ -298,6 +298,26 @@ PROTOTYPES.update({
     "amg_cf_pmis": (_i, [_i, _i, _ip, _ip, C.c_ulonglong, _ip]),
     "amg_classical_interp": (_i, [_i, _i, _ip, _ip, _dp, _ip, _ip, _ip, _i, _i, C.POINTER(AmgHostCsr)]),
     "amg_set_setup_scratch": (_i, [_ll]),
+    # several right-hand sides at once
+    "amg_mvec_create": (_i, [_p, _i, _i, _pp]),
+    "amg_mvec_free": (_i, [_p]),
+    "amg_mvec_size": (_i, [_p, _ip, _ip]),
+    "amg_mvec_upload": (_i, [_p, _p, _dp]),
+    "amg_mvec_download": (_i, [_p, _p, _dp]),
+    "amg_mvec_set_col": (_i, [_p, _p, _i, _p]),
+    "amg_mvec_get_col": (_i, [_p, _p, _i, _p]),
+    "amg_mvec_set": (_i, [_p, _p, _d]),
+    "amg_mvec_axpy": (_i, [_p, _dp, _p, _p]),
+    "amg_mvec_dot": (_i, [_p, _p, _p, _dp]),
+    "amg_mvec_norm2": (_i, [_p, _p, _dp]),
+    "amg_mrhs_spgemv": (_i, [_p, _p, _p, _p, _d, _d, _p, _i, _i]),
+    "amg_mrhs_matvec": (_i, [_p, _p, _p, _p]),
+    "amg_mrhs_jacobi": (_i, [_p, _p, _p, _p, _p, _d, _i, _i]),
+    "amg_mrhs_l1_jacobi": (_i, [_p, _p, _p, _p, _p, _p, _i, _i]),
+    "amg_mrhs_precond_apply": (_i, [_p, _p, _p]),
+    "amg_mrhs_solve": (_i, [_p, _p, _p, _dp, _ip]),
+    "amg_mrhs_pcg_solve": (_i, [_p, _p, _p, _dp, _ip]),
+    "amg_mrhs_pcg_scalars": (_i, [_p, _i, _dp, _dp, _dp, _i, _ip]),
 })
 
 

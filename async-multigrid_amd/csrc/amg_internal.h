@@ -250,6 +250,32 @@ struct amg_vec {
    bool owns = true;
 };
 
+// n x k fp64, row-major: element (i, j) at d[i * k + j]; k is 2, 4 or 8
+struct amg_mvec {
+   amg_ctx *ctx = nullptr;
+   int n = 0, k = 0;
+   double *d = nullptr;
+};
+
+// what the multi-vector cycle (amg_mrhs.cpp) reads of a hierarchy (amg_solver.cpp): the
+// level operators, the L1 row norms, the options as they stand now, and the slot of the
+// hierarchy's multi-vector state, which amg_hier_free hands to amg_mrhs_state_free
+struct amg_mrhs_state;
+struct amg_hier_level_view {
+   const amg_mat *A, *P, *R;
+   int n;
+   const double *l1;
+};
+struct amg_hier_view {
+   amg_ctx *ctx;
+   int L;
+   const amg_opts *o;
+   amg_mrhs_state **mrhs;
+   std::vector<amg_hier_level_view> lv;
+};
+void amg_hier_get_view(amg_hier *H, amg_hier_view *out);
+void amg_mrhs_state_free(amg_mrhs_state *st);
+
 // workspace
 int amg_ctx_partials(amg_ctx *ctx, size_t n, double **out);
 // device CSR allocation (+ diagonal extraction) for in-library builders
@@ -544,6 +570,44 @@ void pcg_beta_ranks(hipStream_t s, const double *v, int nranks, double *sc, doub
                     double *ring_rho, int first);
 // p = z + sc[BETA] p
 void pcg_update_p(hipStream_t s, const double *z, double *p, int n, const double *sc);
+
+// ---- several right-hand sides at once (amg_mrhs.hip) ---------------------------------
+// Every vector is n x K row-major (amg_mvec), K in {2, 4, 8}; per column the arithmetic
+// of the single-vector launcher of the same name.  The row operators read A's plain CSR
+// arrays (rowptr, col, val), once per launch for all K columns.
+constexpr int MRHS_MAXK = 8;
+inline bool mrhs_width_ok(int K) { return K == 2 || K == 4 || K == 8; }
+// y[rb, re) per the Gemv mode; b may alias y, x may not
+void mrhs_spgemv(hipStream_t s, int K, const amg_mat *A, const double *x, const double *b, const Gemv &g,
+                 double *y, int rb, int re);
+// out = x + (omega (f - A x)) / a_ii where a_ii != 0 (l1: x + (f - A x) / l1[i]), all rows
+void mrhs_jacobi_sweep(hipStream_t s, int K, const amg_mat *A, const double *f, const double *x,
+                       const double *l1, double omega, double *out);
+// jacobi_zero variant 0 on n rows: u = omega f / a where a != 0 | u = f / l1
+void mrhs_jacobi_zero(hipStream_t s, int K, const double *diag, const double *f, const double *l1, double omega,
+                      double *u, int n);
+void mrhs_set(hipStream_t s, double *y, double a, long long len);
+void mrhs_set_col(hipStream_t s, int K, int j, const double *x, double *v, int n); // v(:, j) = x
+void mrhs_get_col(hipStream_t s, int K, int j, const double *v, double *x, int n); // x = v(:, j)
+struct MrhsScal {
+   double a[MRHS_MAXK];
+};
+void mrhs_axpy(hipStream_t s, int K, const MrhsScal &alpha, const double *x, double *y, int n);
+// column j's partials of x . y (y null: x . x) on dot_partials' grid at part[1024 j ..]
+void mrhs_dot_partials(hipStream_t s, int K, const double *x, const double *y, int n, double *part, int *nparts);
+// out[j] = the sum of column j's partials in reduce_partials' order (do_sqrt: its root)
+void mrhs_reduce_partials(hipStream_t s, int K, const double *part, int np, double *out, int do_sqrt);
+// the PCG scalar block of K columns: scalar q of column j at sc[MRHS_MAXK q + j]; the
+// quotient rules are pcg_alpha_q / pcg_beta_q per column.  ring_*: column j's entry at
+// ring_*[PCG_RING j]; norm: K contiguous values
+void mrhs_pcg_alpha(hipStream_t s, int K, const double *part, int np, double *sc, double *ring_alpha);
+void mrhs_pcg_beta(hipStream_t s, int K, const double *part_rr, const double *part_rz, int np, double *sc,
+                   double *norm, double *ring_beta, double *ring_rho, int first);
+// x += alpha_j p; r -= alpha_j q; the partials of r . r as mrhs_dot_partials lays them
+void mrhs_pcg_update_xr(hipStream_t s, int K, double *x, const double *p, double *r, const double *q, int n,
+                        const double *sc, double *part, int *nparts);
+// p = z + beta_j p
+void mrhs_pcg_update_p(hipStream_t s, int K, const double *z, double *p, int n, const double *sc);
 
 // CG-Lanczos eigenvalue estimate (amg_eig.hip; the recurrence is amg_eig.h): CG on A
 // preconditioned by its diagonal d (null: d = 1, no division), no right-hand side and no

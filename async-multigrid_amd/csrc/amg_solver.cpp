@@ -119,9 +119,22 @@ struct amg_hier {
    // preconditioned CG (amg_pcg_*): r lives in r0 and z in lv[0].u, where the
    // cycle reads and leaves them; the rest is allocated by the first amg_pcg_start
    AmgPcg pcg;
+   // the multi-vector entry points' own state (amg_mrhs.cpp), apart from everything above
+   amg_mrhs_state *mrhs = nullptr;
    std::vector<void *> allocs;
    AmgProfLog prof;
 };
+
+// the accessor of amg_mrhs.cpp: the level operators, the options and the state slot
+void amg_hier_get_view(amg_hier *H, amg_hier_view *out)
+{
+   out->ctx = H->ctx;
+   out->L = H->L;
+   out->o = &H->o;
+   out->mrhs = &H->mrhs;
+   out->lv.clear();
+   for (const Level &v : H->lv) out->lv.push_back({v.A, v.P, v.R, v.n, v.l1});
+}
 
 static int dalloc(amg_hier *H, size_t n, double **p)
 {
@@ -465,6 +478,7 @@ extern "C" int amg_hier_free(amg_hier *H)
    hipStreamSynchronize(H->ctx->stream);
    for (auto s : H->ctx->level_streams) hipStreamSynchronize(s);
    graphs_reset(H);
+   amg_mrhs_state_free(H->mrhs);
    for (void *p : H->allocs) hipFree(p);
    for (auto &l : H->lv) hipFree(l.d_blk);
    delete H;

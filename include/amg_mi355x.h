@@ -1147,6 +1147,65 @@ int amg_classical_interp(int device, int n, const int *rowptr, const int *col, c
  * on it.  slots < 0: AMG_ERR_ARG. */
 int amg_set_setup_scratch(long long slots);
 
+/* ---- several right-hand sides at once (csrc/amg_mrhs.hip, csrc/amg_mrhs.cpp; no
+ * reference counterpart: the reference solves one system per run) ------------------
+ * A multivector is an n x k fp64 array on the device, row-major: element (i, j) at
+ * i * k + j, a row's k values contiguous.  k is 2, 4 or 8 (else AMG_ERR_ARG).  The
+ * operators below read the plain CSR arrays of a matrix once per launch for all k
+ * columns (whatever compressed forms the matrix also carries) and do, per column,
+ * exactly the arithmetic of the single-vector entry point they are named after: column
+ * j of every result carries the bits of that entry point applied to column j.
+ * Out of scope: additive and asynchronous solvers, BPX, the hybrid JGS and Gauss-Seidel
+ * smoothers, Chebyshev acceleration, the distributed hierarchy, compressed matrix forms
+ * under the multi-vector kernels, widths other than 2, 4 and 8. */
+typedef struct amg_mvec amg_mvec;
+int amg_mvec_create(amg_ctx *ctx, int n, int k, amg_mvec **out);
+int amg_mvec_free(amg_mvec *v);
+int amg_mvec_size(const amg_mvec *v, int *n, int *k);
+int amg_mvec_upload(amg_ctx *ctx, amg_mvec *v, const double *host);         /* n * k, row-major */
+int amg_mvec_download(amg_ctx *ctx, const amg_mvec *v, double *host);
+int amg_mvec_set_col(amg_ctx *ctx, amg_mvec *v, int j, const amg_vec *x);    /* column j = x     */
+int amg_mvec_get_col(amg_ctx *ctx, const amg_mvec *v, int j, amg_vec *x);    /* x = column j     */
+int amg_mvec_set(amg_ctx *ctx, amg_mvec *v, double alpha);
+/* y(:, j) += alpha[j] x(:, j): amg_vec_axpy's rounding per element; alpha: k host values */
+int amg_mvec_axpy(amg_ctx *ctx, const double *alpha, const amg_mvec *x, amg_mvec *y);
+/* out[j] = x(:, j) . y(:, j) / sqrt(x(:, j) . x(:, j)), each column summed in
+ * amg_vec_dot's order: the bits of amg_vec_dot / amg_vec_norm2 on that column (host sync) */
+int amg_mvec_dot(amg_ctx *ctx, const amg_mvec *x, const amg_mvec *y, double *out);
+int amg_mvec_norm2(amg_ctx *ctx, const amg_mvec *x, double *out);
+/* amg_spgemv per column: y = alpha A x + beta b on rows [rb, re); b may alias y, x may not */
+int amg_mrhs_spgemv(amg_ctx *ctx, const amg_mat *A, const amg_mvec *x, const amg_mvec *b, double alpha,
+                    double beta, amg_mvec *y, int rb, int re);
+int amg_mrhs_matvec(amg_ctx *ctx, const amg_mat *A, const amg_mvec *x, amg_mvec *y); /* y = A x */
+/* amg_jacobi / amg_l1_jacobi per column, variant 0 on all rows; l1 is shared by the columns */
+int amg_mrhs_jacobi(amg_ctx *ctx, const amg_mat *A, const amg_mvec *f, amg_mvec *u, amg_mvec *u_prev,
+                    double omega, int sweeps, int zero_first);
+int amg_mrhs_l1_jacobi(amg_ctx *ctx, const amg_mat *A, const amg_mvec *f, amg_mvec *u, amg_mvec *u_prev,
+                       const amg_vec *l1, int sweeps, int zero_first);
+/* The hierarchy entry points run SMEM_Sync_Parfor_Vcycle (SMEM_Sync_AMG.cpp:8-145) on k
+ * columns at once: solver AMG_MULT with the AMG_JACOBI or AMG_L1_JACOBI smoother,
+ * cheby_flag 0 and AMG_DELAY_NONE; anything else is AMG_ERR_UNSUPPORTED before any launch.
+ * Their level vectors are the hierarchy's own, apart from the single-vector state
+ * (allocated by the first call of a width, freed by amg_hier_free): a running amg_solve_* /
+ * amg_pcg_* is not disturbed by them, nor they by it.
+ * z(:, j) = M^-1 r(:, j): amg_precond_apply per column; no host sync */
+int amg_mrhs_precond_apply(amg_hier *H, const amg_mvec *r, amg_mvec *z);
+/* amg_solve per column.  reshist ((num_cycles + 1) * k doubles, row-major by iteration;
+ * may be NULL) holds the 2-norm of every column's outer residual f - A u, summed in
+ * amg_vec_norm2's order, from a device history.  check_resnorm == 1 reads the k norms
+ * back after every cycle and stops once every column is done: reshist[0][j] == 0 or
+ * reshist[it][j] / reshist[0][j] < tol; any other value runs num_cycles cycles with one
+ * sync at the end. */
+int amg_mrhs_solve(amg_hier *H, const amg_mvec *f, amg_mvec *u, double *reshist, int *cycles_done);
+/* amg_pcg_solve per column: k independent recurrences in lockstep (not block CG), every
+ * statement of amg_pcg_solve's on each column, the per-column alpha, beta and rho on the
+ * device.  reshist and the stop rule as amg_mrhs_solve; a column that is done keeps
+ * iterating with the others. */
+int amg_mrhs_pcg_solve(amg_hier *H, const amg_mvec *f, amg_mvec *x, double *reshist, int *iters_done);
+/* amg_pcg_scalars of column col of the last amg_mrhs_pcg_solve */
+int amg_mrhs_pcg_scalars(const amg_hier *H, int col, double *alpha, double *beta, double *rho, int cap,
+                         int *count);
+
 #ifdef __cplusplus
 }
 #endif
