@@ -492,8 +492,20 @@ extern "C" int amg_hier_set_opts(amg_hier *H, const amg_opts *opts)
            "amg_hier_set_opts: cannot switch between ONE_LEVEL and ALL_LEVELS solvers");
    const bool w = opts->smooth_weight != H->o.smooth_weight;
    const bool t = opts->num_threads != H->o.num_threads || opts->jgs_block_rows != H->o.jgs_block_rows;
+   // BPX keeps its level-0 correction in a pair of its own, which a hierarchy
+   // created for MULT does not have yet (init_vectors clears it per solve)
+   if (opts->solver == AMG_BPX) {
+      if (!H->e0) AMG_TRY(dalloc(H, H->lv[0].n, &H->e0));
+      if (!H->e0_alt) AMG_TRY(dalloc(H, H->lv[0].n, &H->e0_alt));
+   }
    H->o = *opts;
    graphs_reset(H);
+   // a running stationary solve ends here: the sweep its last outer residual
+   // prepared (pre_ready, u_alt) and the residual it skipped (r0_stale) belong
+   // to the old smoother and weight; amg_solve / amg_solve_start begin anew
+   H->have_state = false;
+   H->pre_ready = false;
+   H->post_deferred = false;
    if (w) AMG_TRY(hier_prepare_smoother_arrays(H));
    if (t)
       for (auto &l : H->lv) AMG_TRY(default_blocks(H, l));

@@ -480,6 +480,11 @@ int amg_set_march_tuning(amg_ctx *ctx, int mz_pf, int mz27_pf, int mz_occ, int m
  * replayed; the same kernels with the same arguments, bit-identical.  Off by
  * default; the graphs are dropped when the hierarchy's options or blocks change. */
 int amg_set_graphs(amg_ctx *ctx, int enable);
+/* new options on a live hierarchy: everything but a switch between the ONE_LEVEL
+ * solvers (MULT, BPX) and the ALL_LEVELS ones (AMG_ERR_ARG, nothing changed).
+ * State that depends on the options is rebuilt or allocated here (weighted
+ * diagonals, default blocks, BPX's level-0 correction, cached graphs).  A
+ * running amg_solve_start / amg_solve_iterate sequence ends: start it again. */
 int amg_hier_set_opts(amg_hier *H, const amg_opts *opts);
 /* override level `level`'s hybrid-JGS block partition (thread.A_ns/A_ne) */
 int amg_hier_set_blocks(amg_hier *H, int level, const int *blk, int nblk);

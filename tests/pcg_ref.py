@@ -50,8 +50,9 @@ def dev_dot(x, y):
 
 # ---- hierarchies ----------------------------------------------------------------
 def host_hierarchy(amg, oracle, n, interp=None, levels=None):
-    """(L, {"A": [...], "P": [...], "R": [...]}) of the structured generator's hierarchy as oracle.Csr"""
-    g = amg.Gen(n, interp=amg.AMG_INTERP_LINEAR if interp is None else interp,
+    """(L, {"A": [...], "P": [...], "R": [...]}) of the structured generator's hierarchy as oracle.Csr;
+    n: the cube's edge, or (nx, ny, nz)"""
+    g = amg.Gen(*(n if isinstance(n, tuple) else (n,)), interp=amg.AMG_INTERP_LINEAR if interp is None else interp,
                 **({} if levels is None else {"max_levels": levels}))
     L = g.L
     host = {}
