@@ -144,13 +144,16 @@ __global__ void vi_collect_k(const double *__restrict__ val, long long nnz, unsi
    const long long stride = (long long)gridDim.x * blockDim.x;
    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nnz; i += stride) {
       const unsigned long long key = (unsigned long long)__double_as_longlong(val[i]);
+      // before the repeat filter, which starts out holding this very pattern
+      if (key == DICT_EMPTY) {
+         // the empty marker's own pattern: give up on the table (a bit above any key
+         // count, set and not added, so that no number of such entries wraps it away)
+         atomicOr(count, 1 << 20);
+         return;
+      }
       if (key == last0 || key == last1) continue;
       last1 = last0;
       last0 = key;
-      if (key == DICT_EMPTY) {
-         atomicAdd(count, 1 << 20); // the empty marker's own pattern: give up on the table
-         continue;
-      }
       if (dict_useless(count)) return; // many distinct values: stop reading (keeps registration fast)
       dict_insert(key, slots, count);
    }
@@ -209,6 +212,7 @@ __device__ __forceinline__ unsigned long long dc_key(int off, unsigned char b)
 __global__ void dc_collect_k(const int *__restrict__ rowptr, const int *__restrict__ col,
                              const unsigned char *__restrict__ vidx, int n, unsigned long long *slots, int *count)
 {
+   // the repeat filter starts at DICT_EMPTY, which no key equals: dc_key has 40 bits
    unsigned long long last0 = DICT_EMPTY, last1 = DICT_EMPTY;
    int ml = 0, offrow = 0;
    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -314,6 +318,7 @@ __device__ __forceinline__ unsigned long long rp_key(const unsigned char *__rest
 __global__ void rp_collect_k(const int *__restrict__ rowptr, const unsigned char *__restrict__ didx, int n,
                              unsigned long long *slots, int *rep, int *count)
 {
+   // DICT_EMPTY is no key here either: rp_key's low byte is a length of at most 32
    unsigned long long last = DICT_EMPTY;
    int nbad = 0;
    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {

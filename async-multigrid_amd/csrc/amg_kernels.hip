@@ -4567,7 +4567,7 @@ void spgemv(hipStream_t s, const amg_mat *A, const double *x, const double *b, c
 }
 
 // a marched operator's uniform diagonal d whose reciprocal divides exactly
-// (div_rcp): normal, finite, 2^-40 <= |d| <= 2^40, the odd part of its significand below 2^30 (the
+// (div_rcp): normal, finite, 2^-40 <= |d| < 2^40, the odd part of its significand below 2^30 (the
 // distance of x / d from a rounding midpoint then dwarfs the correction's
 // error); AMG_FAST_DIV=0: off
 static bool fast_div_of(const amg_mat *A, double *d, double *y)
@@ -4583,7 +4583,7 @@ static bool fast_div_of(const amg_mat *A, double *d, double *y)
    if (!std::isnormal(a)) return false;
    int e = 0;
    const double m = std::frexp(std::fabs(a), &e); // [0.5, 1)
-   // |d| in [2^-40, 2^40]: with div_rcp_ok's |x| in [2^-960, 2^960) every
+   // |d| in [2^-40, 2^40): with div_rcp_ok's |x| in [2^-960, 2^960) every
    // quotient x / d and product x * (1/d) stays normal and finite
    if (e < -39 || e > 40) return false;
    unsigned long long sig = (unsigned long long)std::ldexp(m, 53);

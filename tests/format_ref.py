@@ -24,9 +24,11 @@ def value_count(A):
 
 
 def value_index(A):
-    """value_index getter: the table size, 0 above MAX_KEYS values or for no entry
-    at all (not restated: a value with the all-ones bit pattern, the hash table's
+    """value_index getter: the table size, 0 above MAX_KEYS values, for no entry
+    at all, or when some value has the all-ones bit pattern (the hash table's
     empty marker)"""
+    if np.any(A.val.view(np.int64) == -1):
+        return 0
     nd = value_count(A)
     return nd if nd <= MAX_KEYS else 0
 

@@ -33,6 +33,22 @@ def test_value_gates():
     assert format_ref.row_pattern(empty, False) == 0
 
 
+def test_empty_marker_value_turns_the_index_off():
+    """the all-ones bit pattern (a NaN) is the hash table's empty marker: no value index, so no form"""
+    marker = np.uint64(2 ** 64 - 1).view(np.float64)
+    for at in (0, 3, 6):
+        rows = [[(0, 2.0), (1, -1.0)], [(1, 2.0), (0, -1.0), (2, -1.0)], [(2, 2.0), (1, -1.0)]]
+        flat = [(i, j) for i, r in enumerate(rows) for j in range(len(r))]
+        i, j = flat[at]
+        rows[i][j] = (rows[i][j][0], marker)
+        A = csr(rows)
+        assert format_ref.value_count(A) == 3
+        assert format_ref.value_index(A) == 0 and format_ref.dict_index(A) == 0
+    # another NaN is a value like any other
+    A = csr([[(0, 2.0), (1, np.nan)], [(1, 2.0)]])
+    assert format_ref.value_index(A) == 2
+
+
 def test_dictionary_and_row_gates():
     long_row = csr([[(0, 1.0)] + [(c, 2.0) for c in range(1, 32)]] + [[(i, 1.0)] for i in range(1, 40)])
     assert np.diff(long_row.rowptr).max() == format_ref.DC_MAXROW and format_ref.dict_index(long_row) == 32

@@ -20,7 +20,7 @@ as blocks (a row that fell back to CSR form would pass everything else).
 The operands planted for the uniform-diagonal division (-0.0, +0.0, 1e300,
 1e-300) all reach the fallback, but for the diagonal 6.0 none of them can show
 a wrong division: the reciprocal path is exact at omega * 1e300 and
-omega * 1e-300 (div_rcp below, asserted), and a -0.0 quotient cannot show in a
+omega * 1e-300 (div_rcp of tests/div_cases.py, asserted), and a -0.0 quotient cannot show in a
 sweep's output (u_i + q is -0.0 only for u_i = -0.0, which makes the residual
 +0.0).  What tells the two divisions apart is an operand whose quotient is
 subnormal (TINY below), planted next to them.
@@ -29,12 +29,12 @@ import hashlib
 import os
 import subprocess
 import sys
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import bsr_cases as bc
+from div_cases import div_rcp  # csrc/amg_kernels.hip div_rcp restated in exact arithmetic
 from test_gpu_bsr import reg  # registers under given switches and restores the context's
 from test_gpu_kernels import assert_bitwise, _vecs
 
@@ -257,19 +257,6 @@ def test_fp64_blocks_forced(amg, oracle, ctx, crafted):
 
 
 # ---- the uniform diagonal's reciprocal division and its fallback -------------------------------
-def _fma(a, b, c):
-    """fma(a, b, c) in exact arithmetic, rounded once (int / int is correctly rounded)."""
-    v = Fraction(a) * Fraction(b) + Fraction(c)
-    return v.numerator / v.denominator if v else 0.0
-
-
-def div_rcp(x, d):
-    """csrc/amg_kernels.hip div_rcp: the quotient by the reciprocal with one correction step."""
-    y = 1.0 / d
-    q0 = x * y
-    return _fma(_fma(-q0, d, x), y, q0)
-
-
 # omega -> f whose operand omega * f of the division by 6.0 is normal, below 2^-960 (so the
 # kernels must divide truly) and has a reciprocal-path quotient with another last bit
 TINY = {1.0: float.fromhex("0x1.9d2b3ad7f6e0dp-1022"), 0.8: float.fromhex("0x1.cc42c0dcdff14p-1022")}

@@ -4,12 +4,10 @@ long, and degenerate shapes.  Expected counts come from the numpy restatement
 (format_ref); the accepted 256-key matrices give bit-identical SpGEMV and
 Jacobi results to plain CSR.
 
-Not here: a value with the bit pattern of the hash table's empty marker (all
-ones).  It is meant to turn the value index off, but a collector lane's repeat
-filter starts out holding that very pattern, so a lane whose first new value is
-the marker skips it: an 8^3 7-pt operator with one such entry registers with
-value_index == 2.  That is a defect of the collector from before this test was
-written, to be fixed and pinned together."""
+Values with awkward bit patterns: one entry with the pattern of the hash
+table's empty marker (all ones) turns the value index off, wherever it stands;
+signed zeros, infinities, a subnormal and two NaNs of different payloads are
+kept as distinct table entries."""
 import numpy as np
 import pytest
 
@@ -167,3 +165,120 @@ def test_degenerate_shapes(ctx, oracle, name):
         assert forms(M) == (0, 0, 0, 0) and M.master_pattern == 0
     assert M.pair_anchor16 == 0 and M.plane_march == 0 and M.march_points == 0 and M.bsr3 == 0
     M.free()
+
+
+# ---- values with awkward bit patterns ----------------------------------------------------------
+MARKER = np.uint64(2 ** 64 - 1).view(np.float64)  # the hash table's empty marker, read as a double
+
+
+@pytest.mark.parametrize("where", ["first", "middle", "last"])
+def test_empty_marker_value_turns_value_index_off(ctx, oracle, amg, where):
+    """The 8^3 7-pt operator with one entry of the all-ones pattern, at entry 0 (a collector
+    lane's first value, which its repeat filter used to skip: value_index == 2 and every
+    compressed form computing with the largest key instead), in the middle and at the end:
+    plain CSR, and SpGEMV and a Jacobi sweep as the same matrix registered with the value index
+    off (the entry's rows NaN in both, every other row exact)."""
+    L = oracle.laplace_7pt(8)
+    val = L.val.copy()
+    at = {"first": 0, "middle": val.size // 2, "last": val.size - 1}[where]
+    val[at] = MARKER
+    A = oracle.Csr(L.nrows, L.ncols, L.rowptr, L.col, val)
+    assert format_ref.value_count(A) == 3 and format_ref.value_index(A) == 0
+    M = register(ctx, A)
+    try:
+        print("empty marker", where, forms(M), expected(A))
+        assert forms(M) == (0, 0, 0, 0) == expected(A)
+        assert M.master_pattern == 0 and M.plane_march == 0 and M.march_points == 0
+        check_against_plain(ctx, amg, A, M)
+    finally:
+        M.free()
+
+
+NAN_A = np.uint64(0x7FF8000000000001).view(np.float64)
+NAN_B = np.uint64(0x7FF8000000000ABC).view(np.float64)
+SPECIAL = np.array([0.0, -0.0, np.inf, -np.inf, 5e-324, NAN_A, NAN_B, -1.0])
+
+
+def special_operator(oracle, zeros_signed=True):
+    """7-pt operator on 12^3 whose off-diagonals cycle, in storage order, through +0.0, -0.0,
+    +inf, -inf, the smallest subnormal, two quiet NaNs of different payloads and -1.0"""
+    L = oracle.laplace_7pt(12)
+    val = L.val.copy()
+    off = np.ones(val.size, bool)
+    off[L.rowptr[:-1]] = False
+    cyc = SPECIAL.copy()
+    if not zeros_signed:
+        cyc[1] = 0.0
+    val[off] = cyc[np.arange(np.count_nonzero(off)) % cyc.size]
+    return oracle.Csr(L.nrows, L.ncols, L.rowptr, L.col, val)
+
+
+SPECIAL_AB = [(1.0, 0.0), (1.0, -1.0), (-1.0, 1.0)]
+
+
+def special_inputs(n):
+    return [("ones", np.ones(n)), ("uniform", np.random.default_rng(12).uniform(-1, 1, n))]
+
+
+def test_special_values_kept_distinct(ctx, oracle, amg):
+    """Every distinct bit pattern is a table entry of its own (9: the eight off-diagonal values
+    and the diagonal), and every form gives the plain-CSR SpGEMV bit for bit, a NaN meeting a
+    NaN.
+
+    The case does not tell the signed zeros apart: with x = ones or uniform and b = zeros a
+    zero product is added to a sum that holds 6 x_i, an infinity or a NaN, where its sign
+    cannot show; the oracle's outputs for this operator and for a copy with -0.0 replaced by
+    +0.0 are the same bits for every (alpha, beta, x) of the list (computed below and printed,
+    not asserted).  That -0.0 and +0.0 are two table entries is what value_index == 9 says.
+    No row of these outputs is finite (12 rows are infinite for x = ones, 218 for x = uniform,
+    the others NaN): what the comparison can show is a row that should be infinite or NaN and
+    is not, or an infinity of the wrong sign."""
+    A = special_operator(oracle)
+    n = A.nrows
+    assert np.unique(SPECIAL.view(np.uint64)).size == 8
+    assert format_ref.value_count(A) == 9 == format_ref.value_index(A)
+    same, finite = True, []
+    Z = special_operator(oracle, zeros_signed=False)
+    assert format_ref.value_count(Z) == 8
+    for _, x in special_inputs(n):
+        for al, be in SPECIAL_AB:
+            ya = oracle.smem_spgemv(A, x, np.zeros(n), al, be, np.zeros(n))
+            yz = oracle.smem_spgemv(Z, x, np.zeros(n), al, be, np.zeros(n))
+            same &= bool(np.all((ya.view(np.uint64) == yz.view(np.uint64)) | (np.isnan(ya) & np.isnan(yz))))
+            finite.append(int(np.count_nonzero(np.isfinite(ya))))
+    print("signed zeros told apart by the oracle's outputs:", not same, "- finite rows per (x, alpha, beta):", finite)
+    regs = []
+    try:
+        for sw in ({"value_index": 0}, {"dict_index": 0}, {"row_pattern": 0}, {"pair_pattern": 0}, {}):
+            for k, v in sw.items():
+                getattr(ctx, "set_" + k)(v)
+            try:
+                regs.append(register(ctx, A))
+            finally:
+                for k in sw:
+                    getattr(ctx, "set_" + k)(1)
+        plain, vi_only, dc_only, rp_only, full = regs
+        print("special values", [forms(M) for M in regs], expected(A))
+        assert forms(plain) == (0, 0, 0, 0)
+        for M in regs[1:]:
+            assert M.value_index == 9
+        assert vi_only.dict_index == 0 and dc_only.dict_index > 0 and dc_only.row_pattern == 0
+        assert rp_only.pair_pattern == 0 and forms(full) == expected(A)
+        for tag, x in special_inputs(n):
+            xv, bv = ctx.vec(x), ctx.vec(n)
+            for al, be in SPECIAL_AB:
+                ref = oracle.smem_spgemv(A, x, np.zeros(n), al, be, np.zeros(n))
+                outs = []
+                for M in regs:
+                    y = ctx.vec(n)
+                    amg.smem.SMEM_SpGEMV(ctx, M, xv, bv, al, be, y, 0, n)
+                    outs.append(y.download())
+                    y.free()
+                assert_bitwise(outs[0], ref, f"plain CSR vs oracle, x {tag}, {al} {be}")
+                for k, o in enumerate(outs[1:]):
+                    assert_bitwise(o, outs[0], f"form {k + 1} vs plain CSR, x {tag}, {al} {be}")
+            xv.free()
+            bv.free()
+    finally:
+        for M in regs:
+            M.free()
